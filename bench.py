@@ -1,6 +1,9 @@
 """bench.py -- rendered rays/sec (fwd+bwd) of the differentiable SDF renderer hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times exactly K steps and prints the result line (roofline, cpu_baseline, refine and extras null).
+  --full adds every other measurement described below (the kernel-duration pass behind `roofline`, the CPU baseline, the refinement
+  sections, bench_extras.json).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32).
   (N>1: one rank per GPU over RCCL.  Under torch.distributed.run the ranks read RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env; started
    as a plain `python bench.py --gpus N` the script re-launches ITSELF as N ranks (sdflabel_amd/launch.py) and refuses to run if the node has
    fewer than N GPUs -- an N-GPU line is never produced by fewer than N ranks; `rccl_ranks` in the line is dist.get_world_size())
@@ -19,7 +22,7 @@ BASELINE.json do not exist in the reference algorithm and are re
 One ray = one pixel of one crop in one step; value = rays of all ranks / max-over-ranks wall time (weak scaling: one crop per
 rank, no data-path collective; the per-crop results are all-gathered once after the timed region).
 
-The printed line (ONE line, < 4 KB, key set pinned by tests/test_host_cpu.py) carries the contract keys: `roofline` for the dominant kernel (the
+The printed line (ONE line, < 4 KB, key set pinned by tests/test_host_cpu.py) carries the contract keys; under --full: `roofline` for the dominant kernel (the
 fused decoder forward, MFMA-bound) timed with events on the launch stream in a separate pass; `cpu_baseline`: the reference's dense algorithm as a
 multi-threaded torch-CPU port (oracle/torch_cpu_port.py, pinned to the reference's golden G7) timed on the host cores for one full crop-iteration
 of the same workload (rank 0, N=1 only); `refine`: crops/s of BASELINE configs[3] -- `--total-crops` (default 1024) crops sharded crop i -> rank
@@ -28,8 +31,8 @@ all_gather of the result rows: the strong-scaling figure of north_star (seconds 
 reference's shipped float16, both with candidate reuse (bit-identical to evaluating every grid row every iteration: DESIGN.md 3.2).
 Everything else goes to bench_extras.json: the same sections evaluating every grid row (`refine_sharded_full_grid`, `refine_sharded_float16_full_grid`),
 `refine_sharded_prefilter`, `refine_sharded_configs4` (512x512 rays, float16), `refine_sharded_traced`, `roofline_splat`, `dropin_api`, `pose_only`,
-`f16_decoder`, `split_decoder`, `prefilter_decoder`, `sphere_trace`, `optimizer_mirror_varied_crops`, per-rank step times.  Under --gpus N > 1 only
-the headline and the two `refine` sections run.
+`f16_decoder`, `split_decoder`, `prefilter_decoder`, `sphere_trace`, `optimizer_mirror_varied_crops`, per-rank step times.  Under --full --gpus N > 1
+only the headline and the two `refine` sections run.
 """
 import argparse
 import json
@@ -189,8 +192,8 @@ def compact_line(full, extras_path=None):
         out[k] = _num(full.get(k))
     cfg = full.get("config") or {}
     out["config"] = {k: _short(cfg.get(k), 200) for k in CONFIG_KEYS if k in cfg}
-    rf = full.get("roofline") or {}
-    out["roofline"] = {k: _num(_short(rf.get(k), 120)) for k in ROOFLINE_KEYS if k in rf}
+    rf = full.get("roofline")
+    out["roofline"] = {k: _num(_short(rf.get(k), 120)) for k in ROOFLINE_KEYS if k in rf} if isinstance(rf, dict) else None
     cb = full.get("cpu_baseline")
     out["cpu_baseline"] = {k: _num(_short(cb.get(k), 240)) for k in CPU_KEYS if k in cb} if isinstance(cb, dict) else None
     # the metric's second half ("refine-demo crops/sec"): the sharded 60-iteration refinement, exact f32 and the reference's shipped f16
@@ -233,9 +236,30 @@ def write_extras(full, path=None):
     return written
 
 
+DUMP_MAX_BYTES = 60 * 10 ** 6          # --dump-outputs: data bytes in all (64 MB with room for the .npy headers)
+DUMP_WHOLE_BYTES = 1 << 20             # arrays up to this size are always written whole
+
+
+def dump_outputs(outdir, arrays, suffix=""):
+    """Write every array of `arrays` as outdir/<name><suffix>.npy in float32.  When they hold more than DUMP_MAX_BYTES in all, each array above
+    DUMP_WHOLE_BYTES is replaced by a sample of its flattened elements: sorted indices drawn without replacement from a generator seeded with
+    the array's name, so that two runs with the same arguments write the same elements."""
+    import zlib
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    whole = sum(a.nbytes for a in arrays.values() if a.nbytes <= DUMP_WHOLE_BYTES)
+    keep = 1.0 if total <= DUMP_MAX_BYTES else (DUMP_MAX_BYTES - whole) / (total - whole)
+    for name, a in arrays.items():
+        if keep < 1.0 and a.nbytes > DUMP_WHOLE_BYTES:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, int(a.size * keep), replace=False))]
+        np.save(os.path.join(outdir, name + suffix + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--extras", default=None, help="where the full record of the run is written (default: bench_extras.json next to bench.py)")
+    ap.add_argument("--extras", default=None, help="with --full: where the full record of the run is written (default: bench_extras.json next to bench.py)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=250)
     ap.add_argument("--warmup", type=int, default=10)
@@ -246,12 +270,18 @@ def main():
     ap.add_argument("--sharded-iters", type=int, default=60, help="refinement iterations per crop in the sharded sections (the reference's "
                     "refinement length, configs/config_refine.ini:15)")
     ap.add_argument("--configs4-crops", type=int, default=256, help="crops of the configs[4]-shaped sharded section (512x512 rays, float16 decoder)")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline loop (+ cpu_baseline): skip the informational sections")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the headline loop (+ cpu_baseline): skip the informational sections")
     ap.add_argument("--line-check", action="store_true", help="with --launch-check: print the compact bench line (canned sections, no "
                     "measurement) instead of the launch report")
     ap.add_argument("--launch-check", action="store_true", help="only bring up the N ranks, all_gather their ranks and print one JSON line "
                     "(plumbing check of the self-launcher; falls back to gloo on a machine without GPUs)")
+    ap.add_argument("--full", action="store_true", help="after the headline, every other measurement: the kernel-duration pass (roofline), the "
+                    "long run, the refinement and informational sections, cpu_baseline, bench_extras.json (default: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (images, front-facing "
+                    "points, counts, gradients) as DIR/<name>.npy in float32; under --gpus N > 1 every rank writes <name>_rank<r>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global H, W
     H = W = int(args.crop_size)
 
@@ -385,12 +415,37 @@ def main():
         per_rank_ms = [float(g.item()) for g in got]
     assert not br.overflow()
     n_surf, n_front = int(br.cnt[0]), int(br.fcnt[0])
-    loss = br.color[0].sum() + br.mask[0].sum() + br.nimg[0].sum() + br.xyzf[0].sum()
     if dist is not None:
         # the path's only exchange: per-crop result rows gathered once, outside the per-iteration critical path
         res = torch.cat([br.color.sum(dim=(1, 2, 3)).view(CB, 1), br.g_yaw.view(CB, 1), br.g_trans, br.g_latent], dim=1).float()
         table = gather_crop_results(res, CB * world, rank, world)
         assert table.shape == (CB * world, 8) and bool(torch.isfinite(table).all())
+    if args.dump_outputs:
+        # what BatchRenderer.forward / backward hand a caller after the last timed step; xyzf: the front-facing rows of every crop, in crop order
+        nf = br.fcnt.tolist()
+        dump_outputs(args.dump_outputs, {
+            "color": br.color.cpu(), "mask": br.mask.cpu(), "depth": br.depth.cpu(), "normals": br.nimg.cpu(),
+            "xyzf": torch.cat([br.xyzf[b, :nf[b]] for b in range(CB)]).cpu(), "nf": br.fcnt.cpu(), "n": br.cnt.cpu(),
+            "g_yaw": br.g_yaw.cpu(), "g_trans": br.g_trans.cpu(), "g_latent": br.g_latent.cpu()}, "_rank%d" % rank if world > 1 else "")
+    rays = H * W * CB * world * args.steps
+    line = {
+        "metric": "rendered rays/sec (fwd+bwd)", "value": rays / dt, "unit": "rays/s", "n_gpus": world, "rccl_ranks": rccl_ranks,
+        "rccl_version": rccl_version, "launcher": launcher, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": ("BASELINE configs[1]: one" if (CB == 1 and H == 256) else ("BASELINE configs[4]-style: %d" % CB if H == 512 else "BASELINE configs[2]-style: %d" % CB)) +
+                               " %dx%d crop(s) per GPU, DeepSDF 8x512 on a 40^3 grid, fwd+bwd to yaw/trans/latent, decoder re-evaluated every step" % (H, W),
+                   "crops_per_gpu": CB, "rays_per_crop": H * W, "grid_points": G, "surfels": int(n_surf),
+                   "front_facing": int(n_front), "march_steps": None, "parallelism": "crop-parallel x%d" % world},
+    }
+    if not args.full:
+        if rank == 0:
+            print(compact_line(line, None), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    loss = br.color[0].sum() + br.mask[0].sum() + br.nimg[0].sum() + br.xyzf[0].sum()
     # ---- a longer run of the same step (>= 200 steps and >= 0.5 s): the headline's 20-250 steps are a 40-500 ms region ----
     long_steps = max(200, int(0.6 / max(dt / args.steps, 1e-6)) + 1)
     gc.collect()
@@ -1027,17 +1082,6 @@ def main():
             dropin["launches"] = {"error": repr(e)[:200]}
 
     if rank == 0:
-        rays = H * W * CB * world * args.steps
-        line = {
-            "metric": "rendered rays/sec (fwd+bwd)", "value": rays / dt, "unit": "rays/s", "n_gpus": world, "rccl_ranks": rccl_ranks,
-            "rccl_version": rccl_version, "launcher": launcher, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": ("BASELINE configs[1]: one" if (CB == 1 and H == 256) else ("BASELINE configs[4]-style: %d" % CB if H == 512 else "BASELINE configs[2]-style: %d" % CB)) +
-                                   " %dx%d crop(s) per GPU, DeepSDF 8x512 on a 40^3 grid, fwd+bwd to yaw/trans/latent, decoder re-evaluated every step" % (H, W),
-                       "crops_per_gpu": CB, "rays_per_crop": H * W, "grid_points": G, "surfels": int(n_surf),
-                       "front_facing": int(n_front), "march_steps": None, "parallelism": "crop-parallel x%d" % world},
-        }
         flops = 2.0 * macs * G * CB
         ach = flops / (mlp_ms * 1e-3) / 1e12
         traffic = None

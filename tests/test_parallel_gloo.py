@@ -170,19 +170,23 @@ def test_refine_sharded_single_rank_without_a_process_group():
 
 # ---- bench.py --gpus N started WITHOUT a launcher must become N ranks (or refuse) ---------------------------------------------------------
 
-def _bench(*argv, timeout=240):
+def _bench(*argv, timeout=240, launch_ranks=None):
+    """launch_ranks: a --launch-check job of that many ranks -- on a node with GPUs, but fewer than that, the child sees no GPU and takes the
+    gloo path of a machine without one (with the GPUs visible it would rightly refuse to start more ranks than GPUs)"""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "SDFR_SELF_LAUNCHED")}
+    if launch_ranks is not None and 0 < torch.cuda.device_count() < launch_ranks:
+        env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = "-1"
     return subprocess.run([sys.executable, os.path.join(root, "bench.py")] + list(argv), capture_output=True, text=True, timeout=timeout, env=env)
 
 
 def test_bench_self_launches_two_ranks_when_started_without_a_launcher():
     """plain `python bench.py --gpus 2 --launch-check`: the script re-launches itself under torch.distributed.run, both ranks join the
-    process group (gloo here: no GPU in this container; RCCL on the GPU box) and rank 0 reports the group's size"""
+    process group (gloo without 2 GPUs; RCCL on a node with 2 or more) and rank 0 reports the group's size"""
     import json
-    r = _bench("--gpus", "2", "--launch-check")
+    r = _bench("--gpus", "2", "--launch-check", launch_ranks=2)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["launch_check"] and line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and line["ranks"] == [0, 1]
@@ -192,7 +196,7 @@ def test_bench_self_launches_two_ranks_when_started_without_a_launcher():
 def test_bench_line_of_a_two_rank_job_is_compact_and_carries_the_rank_count():
     """`--launch-check --line-check`: two gloo ranks, rank 0 prints the line a real run prints (canned sections): parseable, < 4 KB, rccl_ranks 2"""
     import json
-    r = _bench("--gpus", "2", "--launch-check", "--line-check")
+    r = _bench("--gpus", "2", "--launch-check", "--line-check", launch_ranks=2)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "rank 0 alone prints, and one line only"

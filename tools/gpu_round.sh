@@ -6,12 +6,12 @@ TAG=${1:-r06}
 mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -15 > $O/pytest_$TAG.log
-timeout 900 python bench.py --extras $O/bench_extras_$TAG.json > $O/bench_$TAG.json 2> $O/bench_$TAG.err
+timeout 900 python bench.py --full --extras $O/bench_extras_$TAG.json > $O/bench_$TAG.json 2> $O/bench_$TAG.err
 cd /tmp && export TMPDIR=/tmp
 # kernel trace + stats of the headline loop alone (--no-extras: every decoder-forward launch is the single-crop one the roofline is quoted on)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -o trace -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/prof_$TAG.log 2>&1
-# ... and of the whole default run (all informational sections; the sharded refinement shortened: its kernels are the refine_demo's at 64 crops)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/proffull_$TAG -o trace -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --total-crops 128 --configs4-crops 64 > $O/proffull_$TAG.log 2>&1
+# ... and of the whole --full run (all informational sections; the sharded refinement shortened: its kernels are the refine_demo's at 64 crops)
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/proffull_$TAG -o trace -- python $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --total-crops 128 --configs4-crops 64 > $O/proffull_$TAG.log 2>&1
 # the sphere-tracing mode alone (march kernels: decoder forward on the active rows, step kernel, looping tail)
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profsphere_$TAG -o trace -- python $R/tools/sphere_time.py --only f16 --spec 4 > $O/profsphere_$TAG.log 2>&1
 # HBM traffic: separate --pmc passes (FETCH_SIZE and WRITE_SIZE do not fit one pass), headline loop only
