@@ -1,6 +1,7 @@
 // DeepSDF decoder: host side of the C ABI (weight packing, dispatch).  The kernels live in mlp_kernel.h and are instantiated in
 // mlp_fwd32.hip / mlp_fwd16.hip / mlp_jac.hip / mlp_small.hip.
 #include "mlp_kernel.h"
+#include <cmath>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -89,6 +90,23 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
             }
         for (int r = 0; r < L.out_dim; ++r) bias[(size_t)l * HP + r] = h_b[l][r];
     }
+    // k-major image of the exact-f32 grid forward's compacted products (mlp_kernel.h, KC): Wk[k][row] at float offset 4 off_f of the
+    // layer, zero padded like Wf.  Skipping a zero activation is exact only while 0 * w == 0, i.e. for finite weights: a decoder with an
+    // inf or NaN weight keeps the full K chain.
+    std::vector<float> Wk;
+    bool finite = true;
+    if (HP == 512 && !d->has_ln) {
+        Wk.assign((size_t)off_f * 4, 0.f);
+        for (int l = 0; l < n_lin - 1; ++l) {
+            const MlpLayer& L = P.L[l];
+            for (int r = 0; r < L.out_dim; ++r)
+                for (int k = 0; k < L.in_dim; ++k) {
+                    const float w = h_W[l][(size_t)r * L.in_dim + k];
+                    finite = finite && std::isfinite(w);
+                    Wk[(size_t)L.off_f * 4 + (size_t)k * HP + r] = w;
+                }
+        }
+    }
     for (int k = 0; k < in_dim[n_lin - 1]; ++k) wl[k] = h_W[n_lin - 1][k];
     P.b_last = h_b[n_lin - 1][0];
 
@@ -117,6 +135,12 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
     SDFR_HIP_CHECK(hipMemcpy(d->d_Wb, Wb.data(), Wb.size() * sizeof(float), hipMemcpyHostToDevice));
     SDFR_HIP_CHECK(hipMemcpy(d->d_bias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
     SDFR_HIP_CHECK(hipMemcpy(d->d_wlast, wl.data(), wl.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!Wk.empty()) {
+        SDFR_HIP_CHECK(hipMalloc(&d->d_Wk, Wk.size() * sizeof(float)));
+        SDFR_HIP_CHECK(hipMemcpy(d->d_Wk, Wk.data(), Wk.size() * sizeof(float), hipMemcpyHostToDevice));
+        P.Wk = d->d_Wk;
+        P.kcompact = finite ? 1 : 0;
+    }
     P.Wf = d->d_Wf; P.Wb = d->d_Wb; P.Wh = d->d_Wh; P.Ws = d->d_Ws; P.Wbh = d->d_Wbh; P.bias = d->d_bias; P.w_last = d->d_wlast; P.fwd_np = 2;
     *out = d;
     return SDFR_OK;
@@ -129,7 +153,7 @@ extern "C" int sdfr_debug_set_trace(void* device_buffer) { g_trace = (unsigned l
 
 extern "C" int sdfr_decoder_destroy(sdfr_decoder* d) {
     if (!d) return SDFR_OK;
-    void* bufs[] = {d->d_Wf, d->d_Wb, d->d_Wh, d->d_Ws, d->d_Wbh, d->d_bias, d->d_wlast, d->d_lng, d->d_lnb, d->ln_ws};
+    void* bufs[] = {d->d_Wf, d->d_Wb, d->d_Wk, d->d_Wh, d->d_Ws, d->d_Wbh, d->d_bias, d->d_wlast, d->d_lng, d->d_lnb, d->ln_ws};
     for (void* b : bufs) (void)hipFree(b);
     delete d;
     return SDFR_OK;

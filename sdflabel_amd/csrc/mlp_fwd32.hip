@@ -2,6 +2,7 @@
 // Geometry macros (tools/ab_build.sh A/B builds): SDFR_FWD_FT feature tiles per wave, SDFR_FWD_NW waves (FT*NW = 16), SDFR_FWD_NP point
 // tiles (32 points each) per workgroup, weight-fragment ring SDFR_FWD_PF, activation-fragment ring SDFR_FWD_PFB.
 #include "mlp_kernel.h"
+#include <stdlib.h>
 #ifndef SDFR_FWD_PF
 #define SDFR_FWD_PF 2
 #endif
@@ -20,6 +21,11 @@ void sdfr_launch_fwd_f32_512(const MlpParams& P, int64_t n, bool save_masks, hip
     // one instantiation serves both cases: without a mask buffer the mask-saving kernel skips its stores (measured 1.78 ms against 1.93 ms
     // of a separate no-mask instantiation -- the compiler's schedule for that one is simply worse)
     (void)save_masks;
+    // per-tile K compaction (mlp_kernel.h, KC) is on by default; SDFR_FWD_COMPACT=0 in the environment, read at every launch, runs the full
+    // K chain instead (same bits: A/B timing and the parity tests)
+    MlpParams Q = P;
+    const char* e = getenv("SDFR_FWD_COMPACT");
+    if (e && e[0] == '0') Q.kcompact = 0;
     hipLaunchKernelGGL((sdfr_mlp_kernel<float, 32, SDFR_FWD_FT, SDFR_FWD_NP, SDFR_FWD_NW, SDFR_FWD_PF, 1, SDFR_FWD_PFB>), dim3(grid),
-                       dim3(64 * SDFR_FWD_NW), 0, s, P);
+                       dim3(64 * SDFR_FWD_NW), 0, s, Q);
 }

@@ -47,6 +47,8 @@ struct MlpParams {
     const void* Wh;         // forward image, float16:  [k/8][HP] 8 x half
     const void* Wbh;        // backward (transposed) image, float16:  [j/8][HP] 8 x half (the float16 decoder's mask-fed Jacobian)
     const void* Ws;         // split-forward image: [k/8][HP][2] 8 x half -- hi = half(w) and lo = half((w - hi) * 2^11) side by side
+    const float* Wk;        // exact-f32 forward, k-major image: [layer][k][HP] floats at float offset 4 * off_f (per-tile K compaction, below)
+    int kcompact;           // 1: the exact-f32 grid forward skips features that are zero at every point of a tile (0: the full K chain)
     int kinj;               // half forward image Wh: re-injected input columns sit at k = HP + input column (K-side injection, n_inputs <= 8)
     int fwd_np;             // MODE 3: point tiles per workgroup of the forward launch that saved the masks (2: f32, 4: f16)
     const float* bias;      // [n_mfma][HP]
@@ -117,6 +119,7 @@ struct sdfr_decoder {
     int n_lin, n_inputs, use_tanh, HP;
     float4* d_Wf;
     float4* d_Wb;
+    float* d_Wk;
     void* d_Wh;
     void* d_Ws;
     void* d_Wbh;
@@ -277,6 +280,13 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
     // other seven waves at the barrier for 4-7 k cycles.)
     __shared__ float jinj[MLDS ? PT * 8 : 1];
     __shared__ int jpfx[JPOOL ? 66 : 1];                          // JPOOL: inclusive prefix of the crops' live tiles (B <= 64), [64] = total
+    // KC (per-tile K compaction of the exact-f32 grid forward): a hidden layer's epilogue keeps only the features that are
+    // non-zero at some point of the tile and writes them to consecutive operand slots, in the order in which the full K chain visits them;
+    // the next product walks that shorter list and gathers its weights from the k-major image Wk.  A skipped term is fma(0, w, acc) == acc
+    // (up to the sign of a zero accumulator, which no ReLU output keeps), so every output and mask bit is the full chain's.
+    constexpr bool KC = !HALF && MS == 32 && FT == 2 && NP == 2 && NW == 8 && (MODE == 0 || MODE == 1) && !LN && XF == 0;
+    __shared__ int4 kc_list4[KC ? HP / 4 : 1];                    // operand slot -> k * HP (element offset of the k-row in Wk)
+    __shared__ int kc_cnt[KC ? NW : 1];                           // surviving features per wave (published by the layer's first barrier)
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -741,6 +751,77 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
             else if (nact > 0) gemm_body(Wl, kpad, nact, std::false_type{});
         }
     };
+    // KC product: the operand holds nk compacted slots (a multiple of 2 KT), slot s = k-tile s / KT, lane group (s % KT) / KV, component
+    // s % KV -- the place where the full chain would have visited its feature.  A lane's weight fragment is gathered as KV dwords of the
+    // k-major image (Wk[k][row]: 32 lanes of a lane group read 128 contiguous bytes per load); the k list is read from LDS one tile ahead of
+    // the gather it feeds.  Ring of two tiles and clamped prefetch indices, as in gemm_body's branch-free loop.
+    auto gemm_kc_body = [&](const float* __restrict__ Wl, int nk, int nact, auto full_tag) {
+        constexpr bool FULL = decltype(full_tag)::value;
+        const int nkt = nk / KT;
+        if (nkt <= 0) return;
+        const float* wp = Wl + fbase + lp;
+        const vec_t* bptr = act + lg * PT + lp;
+        const int4* klp = kc_list4 + lg;
+        vec_t a[2][FT], b[2][NP];
+        int4 ko[2];
+        auto load_a = [&](const int4& k, vec_t* aa) {
+#pragma unroll
+            for (int f = 0; f < FT; ++f)
+                if (FULL || f < nact) {
+                    aa[f][0] = wp[k.x + f * MS]; aa[f][1] = wp[k.y + f * MS]; aa[f][2] = wp[k.z + f * MS]; aa[f][3] = wp[k.w + f * MS];
+                } else {
+#pragma unroll
+                    for (int i = 0; i < KV; ++i) aa[f][i] = (ET)0;
+                }
+        };
+        auto load_b = [&](int tile, vec_t* bb) {
+            const vec_t* bp = bptr + tile * (NLG * PT);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) bb[p] = bp[p * MS];
+        };
+        auto mma = [&](const vec_t* aa, const vec_t* bb) {
+#pragma unroll
+            for (int ks = 0; ks < M::NSTEP; ++ks)
+#pragma unroll
+                for (int f = 0; f < FT; ++f)
+                    if (FULL || f < nact) {
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) acc[f][p] = M::step(aa[f], bb[p], acc[f][p], ks);
+                    }
+        };
+        const int last = nkt - 1;
+        ko[0] = klp[0];
+        load_a(ko[0], a[0]);
+        load_b(0, b[0]);
+        ko[1] = klp[min(1, last) * NLG];
+        for (int t = 0; t < nkt; t += 2) {
+            load_a(ko[1], a[1]);
+            load_b(min(t + 1, last), b[1]);
+            ko[0] = klp[min(t + 2, last) * NLG];
+            __builtin_amdgcn_sched_barrier(0);
+            mma(a[0], b[0]);
+            __builtin_amdgcn_sched_barrier(0);
+            load_a(ko[0], a[0]);
+            load_b(min(t + 2, last), b[0]);
+            ko[1] = klp[min(t + 3, last) * NLG];
+            __builtin_amdgcn_sched_barrier(0);
+            mma(a[1], b[1]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    auto gemm_kc = [&](auto Wl, int nk, int rows_active) {            // (generic: instantiated by KC kernels only)
+#pragma unroll
+        for (int f = 0; f < FT; ++f)
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+                for (int r = 0; r < RG * 4; ++r) acc[f][p][r] = 0.f;
+        int nact = (rows_active - fbase + MS - 1) / MS;
+        nact = nact < 0 ? 0 : (nact > FT ? FT : nact);
+        nact = __builtin_amdgcn_readfirstlane(nact);
+        if (nact == FT) gemm_kc_body(Wl, nk, FT, std::true_type{});
+        else if (nact > 0) gemm_kc_body(Wl, nk, nact, std::false_type{});
+    };
     // first feature of the 4-register group rg of feature tile f held by this lane
     auto feat0 = [&](int f, int rg) { return fbase + f * MS + rg * (4 * NLG) + 4 * lg; };
     const vec_t* Wfwd = reinterpret_cast<const vec_t*>(HALF ? (const void*)P.Wh : (const void*)P.Wf);
@@ -825,12 +906,20 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
 
     // ---- forward through the MFMA layers -------------------------------------------------------------------
     int* t_more = reinterpret_cast<int*>(gy);           // gy is unused by forward modes
+    const bool kc_on = KC && P.kcompact && P.Wk;
+    int kc_n = 0;                                       // KC: compacted K extent of the operand the next product reads
     do {
     for (int l = 0; !GMASK && l < P.n_mfma; ++l) {
         const MlpLayer L = P.L[l];
         const MlpLayer Ln = P.L[l + 1];
+        // KC: layer 0 reads the input rows, the last hidden layer writes the full operand of the last linear (its VALU dot product and tanh
+        // keep their partition and bits)
+        const bool kc_in = kc_on && l > 0, kc_out = kc_on && l + 1 < P.n_mfma;
         SDFR_STAMP(l, 0);
-        gemm(Wfwd + (HALF ? L.off_h : L.off_f), HALF ? L.kp_h : L.kp_f, L.out_dim);
+        if constexpr (KC) {
+            if (kc_in) gemm_kc(P.Wk + (int64_t)L.off_f * 4, kc_n, L.out_dim);
+            else gemm(Wfwd + L.off_f, L.kp_f, L.out_dim);
+        } else gemm(Wfwd + (HALF ? L.off_h : L.off_f), HALF ? L.kp_h : L.kp_f, L.out_dim);
         SDFR_STAMP(l, 1);
         // all bias vectors of this lane are requested before the barrier, so their L2 latency overlaps the wait for the other waves
         // (left inside the store loop the compiler serialises them: one exposed round trip per register group)
@@ -840,22 +929,111 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
         for (int f = 0; f < FT; ++f)
 #pragma unroll
             for (int rg = 0; rg < RG; ++rg) b4s[f][rg] = *reinterpret_cast<const float4*>(bias + feat0(f, rg));
-        if (!DBUF) __syncthreads();                       // every wave is done reading act (two operand tiles: the epilogue writes the other one)
-        SDFR_STAMP(l, 2);
         uint32_t mw[MW];
 #pragma unroll
         for (int w = 0; w < MW; ++w) mw[w] = 0u;
         const int inj_lo = L.out_dim, inj_hi = L.out_dim + Ln.inj_n;
-        bool lnl = false;
-        if constexpr (LN) {
-            lnl = L.ln != 0;
-            if (lnl) ln_forward(l, L.out_dim);          // acc already holds gamma * x_hat + beta (bias included)
-        }
         // Re-injected input columns (latent_in / xyz_in_all) occupy a few features of ONE wave in ONE or few layers: whether this wave's
         // feature block touches them is a scalar question, asked once, so that every other wave and layer runs an epilogue without the
         // per-group lane-divergent range checks (32 saveexec/branch pairs per layer otherwise).
         const bool inj_here = __builtin_amdgcn_readfirstlane((int)((Ln.inj_n > 0) && !(KGX > KG && P.kinj) && (fbase + MS * FT > inj_lo) &&
                                                                     (fbase < inj_hi))) != 0;
+        // KC, before the barrier: the layer's outputs in place (bias, ReLU, mask bits, re-injected columns) and the wave's 64-bit chain mask --
+        // bit 2q + g for the feature of register q = (f * RG + rg) * 4 + i of lane group g (feature fbase + f MS + rg 8 + 4 g + i), i.e. the
+        // position at which the full K chain visits it inside the wave's 64 k (k tile, component, lane group).  A feature survives when it is
+        // non-zero at some point of the tile; re-injected input columns always do.  kc_cnt[wave] = survivors, published by the barrier.
+        uint64_t kc_cm = 0ull;
+        auto kc_values = [&](auto inj_tag) {
+            constexpr bool INJ = decltype(inj_tag)::value;
+#pragma unroll
+            for (int f = 0; f < FT; ++f)
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg) {
+                    const int j0 = feat0(f, rg);
+                    const float4 b4 = b4s[f][rg];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const bool inj = INJ && j0 + i >= inj_lo && j0 + i < inj_hi;
+                        bool nz = inj;
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) {
+                            const float x = acc[f][p][rg * 4 + i] + f4c(b4, i);
+                            const bool pos = x > 0.f;
+                            float v = pos ? x : 0.f;
+                            if (SAVE) {
+                                const int bit = ((f * NP + p) * RG + rg) * 4 + i;
+                                mw[bit >> 5] |= (pos ? 1u : 0u) << (bit & 31);
+                            }
+                            if (INJ && inj) v = P.inputs[(int64_t)rows[p * MS + lp] * NI + Ln.inj_off + (j0 + i - inj_lo)];
+                            acc[f][p][rg * 4 + i] = v;
+                            nz = nz || v != 0.f;
+                        }
+                        const uint64_t bal = __ballot(nz);
+                        const int q = (f * RG + rg) * 4 + i;
+                        kc_cm |= ((uint64_t)((uint32_t)bal != 0u) << (2 * q)) | ((uint64_t)((bal >> 32) != 0ull) << (2 * q + 1));
+                    }
+                }
+        };
+        if constexpr (KC) {
+            if (kc_out) {
+                if (inj_here) kc_values(std::true_type{});
+                else kc_values(std::false_type{});
+                if (lane == 0) kc_cnt[wave] = __popcll(kc_cm);
+            }
+        }
+        if (!DBUF) __syncthreads();                       // every wave is done reading act (two operand tiles: the epilogue writes the other one)
+        SDFR_STAMP(l, 2);
+        bool lnl = false;
+        if constexpr (LN) {
+            lnl = L.ln != 0;
+            if (lnl) ln_forward(l, L.out_dim);          // acc already holds gamma * x_hat + beta (bias included)
+        }
+        // KC, after the barrier: the survivors of the waves in front of this one give its first chain position; survivor number `pos` of
+        // the layer goes to operand slot (pos / KT) KT + (pos % 2) KV + (pos % KT) / 2 -- k tile, lane group, component of the full chain's
+        // order -- and the k list gets its weight row.  The last wave pads the list to a multiple of 2 KT with zero activations (k = 0).
+        auto kc_store = [&]() {
+            int off = 0, tot = 0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                const int c = kc_cnt[w];
+                off += w < wave ? c : 0;
+                tot += c;
+            }
+            off = __builtin_amdgcn_readfirstlane(off);
+            tot = __builtin_amdgcn_readfirstlane(tot);
+            auto slot_of = [](int pos) { return (pos & ~(KT - 1)) | ((pos & 1) * KV) | ((pos & (KT - 1)) >> 1); };
+#pragma unroll
+            for (int f = 0; f < FT; ++f)
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int q = (f * RG + rg) * 4 + i;
+                        const int below = __popcll(kc_cm & ((1ull << (2 * q)) - 1ull));
+                        const bool b0 = (kc_cm >> (2 * q)) & 1ull, b1 = (kc_cm >> (2 * q + 1)) & 1ull;
+                        if (lg ? b1 : b0) {
+                            const int s = slot_of(off + below + ((lg && b0) ? 1 : 0));
+#pragma unroll
+                            for (int p = 0; p < NP; ++p) act_e[((s / KV) * PT + p * MS + lp) * KV + (s % KV)] = acc[f][p][rg * 4 + i];
+                        }
+                    }
+            {   // k list: lane (g, q) enters the feature of register q, lane group g
+                const int q = lp, cl = 2 * q + lg;
+                if ((kc_cm >> cl) & 1ull) {
+                    const int j = fbase + (q >> 4) * MS + ((q >> 2) & 3) * (4 * NLG) + 4 * lg + (q & 3);
+                    reinterpret_cast<int*>(kc_list4)[slot_of(off + __popcll(kc_cm & ((1ull << cl) - 1ull)))] = j * HP;
+                }
+            }
+            const int padded = (tot + 2 * KT - 1) & ~(2 * KT - 1);
+            if (wave == NW - 1) {
+                for (int e = 0; e < padded - tot; ++e) {
+                    const int s = slot_of(tot + e);
+                    act_e[((s / KV) * PT + lane) * KV + (s % KV)] = 0.f;          // (PT == 64: lane = point)
+                    if (lane == e) reinterpret_cast<int*>(kc_list4)[s] = 0;
+                }
+            }
+            kc_n = padded;
+        };
         auto epilogue = [&](auto inj_tag) {
             constexpr bool INJ = decltype(inj_tag)::value;
 #pragma unroll
@@ -943,6 +1121,7 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
             else epilogue_half_fast();
 #endif
         }
+        else if (KC && kc_out) kc_store();
         else if (inj_here) epilogue(std::true_type{});
         else epilogue(std::false_type{});
         if (LMASK) {
