@@ -34,11 +34,11 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 400        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 401        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
- * sdfr_mlp_forward_candidates, sdfr_candidate_band, sdfr_losses_fused, sdfr_splat_backward_x, sdfr_pose_latent_solver).  A caller built
+ * sdfr_mlp_forward_candidates, sdfr_candidate_band, sdfr_losses_fused, sdfr_splat_backward_x, sdfr_pose_latent_solver; 401: the RANSAC pose initialisation sdfr_ransac_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -632,6 +632,37 @@ int sdfr_trace_refine_backward(const float* pose, const float* Kinv, int L, int 
  * W1 [3][L], W2 [3][3], W3 [1][3] row-major as nn.Linear stores them.  Returned by Decoder.forward next to the SDF values; unused by the loop. */
 int sdfr_scale_net(const float* latent_row, int L, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
                    const float* b3, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * RANSAC pose initialisation  --  replaces PoseEstimator.init_pose_3d (utils/pose.py:85-233, type 'kabsch' / 'procrustes') for B crops.
+ *
+ * Model (the decoder's surface points and their NOCS colours) and scene (reprojected NOCS points and colours) are ragged:
+ * model / model_cls [B][mcap][3] with mcnt[b] >= 1 rows, scene / scene_cls [B][ncap][3] with ncnt[b] rows, all float32.  A float16 model
+ * is passed widened to float32 (exact) with model_f16 = 1: the fits then round the model's means and centred values to float16 as numpy
+ * does.  For 'kabsch' the caller has already scaled the model by scale_model in its own dtype (utils/pose.py:126-127).
+ * T hypotheses (the reference: 567), 4 distinct scene indices each.
+ */
+/* bytes of the workspace of sdfr_ransac_pose (colour-NN distances, hypothesis transforms, pass lists, inlier mask) */
+int64_t sdfr_ransac_ws_bytes(int B, int ncap, int T);
+/* device sampler: idx [B][T][4] int32 = 4 distinct indices in [0, ncnt[b]) per hypothesis (all zero when ncnt[b] < 4), from a
+ * counter-based hash of (seed, keys[b], t, draw, attempt); keys (DEVICE pointer, int64[B]) == NULL means key b.  A crop's draws depend on
+ * its own key only.  idx must be 16-byte aligned (written as int4). */
+int sdfr_ransac_sample(int64_t seed, const int64_t* keys, const int32_t* ncnt, int B, int T, int32_t* idx, void* stream);
+/* The whole estimate: colour-NN table, gate + fit of every hypothesis, inlier counts, first best, final fit model -> scene.
+ *   idx        [B][T][4] the sampled scene indices (e.g. the reference's np.random.choice draws), or NULL: the device sampler with
+ *              (seed, keys) writes them to idx_out first (keys: DEVICE pointer, int64[B], or NULL = key b); idx and idx_out must be
+ *              16-byte aligned (read / written as int4)
+ *   type       0 kabsch (final scale = scale_model), 1 procrustes (final scale from the fit)
+ *   h_thr      HOST pointer, double[2] = metric_distance_threshold, nocs_distance_threshold (the reference's Python floats)
+ *   ws         sdfr_ransac_ws_bytes(B, ncap, T) bytes
+ * outputs:  found[b] (0 = the reference returns None: ncnt < 5, fewer than 5 best inliers, or a rank-deficient final procrustes),
+ *   best[b] (winning hypothesis, -1 if none), n_inliers[b], scale[b], rot [B][3][3], tra [B][3];
+ *   cnn_idx [B][ncap] nearest model colour per scene point; gate [B][T] bit 0 colour gate passed, bit 1 fit accepted (scored),
+ *   bit 2 rank-deficient sample (s2/s1 < 1e-3); counts [B][T] inlier count per scored hypothesis, -1 otherwise. */
+int sdfr_ransac_pose(const float* model, const float* model_cls, const int32_t* mcnt, int mcap, int model_f16, const float* scene,
+                     const float* scene_cls, const int32_t* ncnt, int ncap, int B, const int32_t* idx, int64_t seed, const int64_t* keys,
+                     int T, int type, float scale_model, const double* h_thr, void* ws, int32_t* found, int32_t* best, int32_t* n_inliers,
+                     float* scale, float* rot, float* tra, int32_t* cnn_idx, int32_t* gate, int32_t* counts, int32_t* idx_out, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

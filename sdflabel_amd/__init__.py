@@ -12,5 +12,7 @@ from .deepsdf.networks.deep_sdf_decoder_scale import Decoder  # noqa: F401
 from .batch import BatchRenderer  # noqa: F401
 from .refine import BatchRefiner  # noqa: F401
 from .renderer.sphere_tracer import SphereTracer  # noqa: F401
+from .pose import ransac_pose  # noqa: F401
+from .pipelines.pose import PoseEstimator  # noqa: F401
 
-__all__ = ["Grid3D", "Rasterer", "Decoder", "setup_dsdf", "BatchRenderer", "BatchRefiner", "SphereTracer", "lib", "SdfrError", "LIB_PATH"]
+__all__ = ["Grid3D", "Rasterer", "Decoder", "setup_dsdf", "BatchRenderer", "BatchRefiner", "SphereTracer", "ransac_pose", "PoseEstimator", "lib", "SdfrError", "LIB_PATH"]
