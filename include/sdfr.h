@@ -34,11 +34,12 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 401        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 402        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
- * sdfr_mlp_forward_candidates, sdfr_candidate_band, sdfr_losses_fused, sdfr_splat_backward_x, sdfr_pose_latent_solver; 401: the RANSAC pose initialisation sdfr_ransac_*).  A caller built
+ * sdfr_mlp_forward_candidates, sdfr_candidate_band, sdfr_losses_fused, sdfr_splat_backward_x, sdfr_pose_latent_solver; 401: the RANSAC pose initialisation sdfr_ransac_*; 402: the evaluator's box overlaps sdfr_rotate_iou, sdfr_box3d_iou,
+ * sdfr_image_box_iou).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -663,6 +664,32 @@ int sdfr_ransac_pose(const float* model, const float* model_cls, const int32_t* 
                      const float* scene_cls, const int32_t* ncnt, int ncap, int B, const int32_t* idx, int64_t seed, const int64_t* keys,
                      int T, int type, float scale_model, const double* h_thr, void* ws, int32_t* found, int32_t* best, int32_t* n_inliers,
                      float* scale, float* rot, float* tra, int32_t* cnn_idx, int32_t* gate, int32_t* counts, int32_t* idx_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Box overlaps of the evaluator  --  replace pipelines/rotate_iou.py (numba.cuda) of the reference.
+ *
+ * Pair (n, k) of boxes [N] x query boxes [K] goes to out[n][k] (row-major, K fastest).  All pointers are DEVICE pointers of the current
+ * device.  Dense mode: G == 0, boff / qoff / ooff NULL, out holds out_len >= N * K elements.  Grouped mode (G > 0): group g holds boxes
+ * [boff[g], boff[g+1]) and query boxes [qoff[g], qoff[g+1]) (int32[G + 1] each, non-decreasing, within N and K); only pairs inside a group
+ * are evaluated and group g's block is written row-major at out + ooff[g] (int64[G + 1], out_len elements in all).  A group whose offsets
+ * are out of range or whose block does not fit in out_len writes nothing.  N == 0 or K == 0 launches nothing.  No synchronisation.
+ *
+ * criterion: -1 IoU; 0 intersection / area of the QUERY box (BEV) -- the reference evaluates devRotateIoUEval(qboxes[k], boxes[n]);
+ * 1 intersection / area of the box; any other value: the intersection itself.
+ */
+/* rotated BEV IoU, float32 boxes [x, y, dx, dy, angle] (rotate_iou.py:22-286); out float32 */
+int sdfr_rotate_iou(const float* boxes, int N, const float* qboxes, int K, int G, const int32_t* boff, const int32_t* qoff,
+                    const int64_t* ooff, int criterion, float* out, int64_t out_len, void* stream);
+/* 3-D IoU, float64 boxes [x, y, z, d0, d1, d2, ry]: the BEV intersection (criterion 2) of columns [0, 2, 3, 5, 6] (camera_frame != 0) or
+ * [0, 1, 3, 4, 6] in float32, then d3_box_overlap_kernel (rotate_iou.py:328-355) in float64 rounded to float32; here criterion 0 divides
+ * by the BOX's volume and 1 by the query box's, as that kernel does.  rinc: NULL (the BEV intersection is computed), or the caller's
+ * float32 BEV intersections laid out as out (d3_box_overlap_kernel on given rinc; may be out itself).  out float32 */
+int sdfr_box3d_iou(const double* boxes, int N, const double* qboxes, int K, int G, const int32_t* boff, const int32_t* qoff,
+                   const int64_t* ooff, int criterion, int camera_frame, const float* rinc, float* out, int64_t out_len, void* stream);
+/* axis-aligned image-box IoU, float64 [x1, y1, x2, y2] (image_box_overlap, rotate_iou.py:358-379; no +1 pixel convention); criterion 0
+ * divides by the box's area, 1 by the query box's; out float64 */
+int sdfr_image_box_iou(const double* boxes, int N, const double* qboxes, int K, int G, const int32_t* boff, const int32_t* qoff,
+                       const int64_t* ooff, int criterion, double* out, int64_t out_len, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */
