@@ -209,8 +209,7 @@ class BatchRefiner:
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream(self.dev))
         snap = (self.params.clone(), self.adam_m.clone(), self.adam_v.clone(), self.adam_t.clone())
-        br = self.br
-        guard = (br.violations.clone(), br.margin_dev.clone(), br.max_dev.clone()) if (br is not None and br.guarded) else None
+        guard = self.br.guard_snapshot() if self.br is not None else None
         with torch.cuda.stream(s):
             self.iteration()
         torch.cuda.current_stream(self.dev).wait_stream(s)
@@ -219,8 +218,8 @@ class BatchRefiner:
             self.iteration()
         # warm-up and capture must not advance the optimisation
         self.params.copy_(snap[0]); self.adam_m.copy_(snap[1]); self.adam_v.copy_(snap[2]); self.adam_t.copy_(snap[3])
-        if guard is not None:                   # ... nor feed the two-stage mode's guard counters
-            br.violations.copy_(guard[0]); br.margin_dev.copy_(guard[1]); br.max_dev.copy_(guard[2]); br.age.zero_()
+        if self.br is not None:                 # ... nor feed the guarded modes' counters
+            self.br.guard_restore(guard)
         self._replay = g.replay
         self.captures = getattr(self, "captures", 0) + 1          # (bench / tests: how often this refiner had to capture)
         return g.replay
