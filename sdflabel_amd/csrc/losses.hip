@@ -220,8 +220,12 @@ __device__ __forceinline__ void loss_2d_pixels_block(const int blk, const int b,
         float g0 = 0.f, g1 = 0.f, g2 = 0.f;
         if (nz) {
             any = ((h | w) != 0) ? 1.f : 0.f;                           // `if rendering_nonzero_idxs.sum()` (:214)
-            // every pixel outside the window has weight 0: masked target 0, distance ||r||  (:223-231)
-            float best = sqrtf(r0 * r0 + r1 * r1 + r2 * r2);
+            // every pixel outside the window has weight 0: masked target 0, distance ||r||  (:223-231) -- if the image HAS a pixel of weight
+            // 0, i.e. its farthest corner lies at diam or more from (h, w).  In a crop smaller than that the window holds every pixel and
+            // the minimum runs over its taps alone (the centre tap is always there)
+            const int fh = max(h, H - 1 - h), fw = max(w, W - 1 - w);
+            const bool far = sqrtf((float)(fh * fh) + (float)(fw * fw)) >= diam;
+            float best = far ? sqrtf(r0 * r0 + r1 * r1 + r2 * r2) : FLT_MAX;
             float b0 = 0.f, b1 = 0.f, b2 = 0.f;
 #pragma unroll UNR
             for (int dh = -rad; dh <= rad; ++dh) {
