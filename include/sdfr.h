@@ -34,12 +34,12 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 402        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 403        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
  * sdfr_mlp_forward_candidates, sdfr_candidate_band, sdfr_losses_fused, sdfr_splat_backward_x, sdfr_pose_latent_solver; 401: the RANSAC pose initialisation sdfr_ransac_*; 402: the evaluator's box overlaps sdfr_rotate_iou, sdfr_box3d_iou,
- * sdfr_image_box_iou).  A caller built
+ * sdfr_image_box_iou; 403: the evaluator's statistics sdfr_eval_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -690,6 +690,49 @@ int sdfr_box3d_iou(const double* boxes, int N, const double* qboxes, int K, int 
  * divides by the box's area, 1 by the query box's; out float64 */
 int sdfr_image_box_iou(const double* boxes, int N, const double* qboxes, int K, int G, const int32_t* boff, const int32_t* qoff,
                        const int64_t* ooff, int criterion, double* out, int64_t out_len, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Evaluator statistics  --  replace compute_statistics_jit, get_thresholds, fused_compute_statistics (numba CPU JIT) and scipy's cdist of
+ * the reference's pipelines/detection_3d.py.  All pointers are DEVICE pointers of the current device; nothing synchronises.
+ *
+ * Packed dataset of G frames: frame f holds detections [doff[f], doff[f+1]) of ND and ground truths [goff[f], goff[f+1]) of NG (int32[G + 1]
+ * each) and its match degrees as a row-major block [nd][ng] (detection major, like out[n][k] of the box overlaps with boxes = detections)
+ * at overlaps + ooff[f] (int64[G + 1], ov_len elements in all); ov_f32 != 0: float32 values (BEV, 3-D), converted to float64 before they
+ * are compared, else float64 (image boxes, distances).  A frame whose offsets are out of range contributes nothing.
+ * Columns: dt_score, dt_yaw, dt_alpha [ND], gt_yaw, gt_alpha [NG], dt_bbox [ND][4], all float64.
+ * Combination c = ml * K + k of ML (class, difficulty) pairs and K overlap levels: flags ign_dt int8[ML][ND] and ign_gt int8[ML][NG]
+ * (-1 other class, 0 valid, 1 ignored), min_overlap float64[ML * K] (for the distance metric minus the distance threshold; every test
+ * is a strict >).  max_nd: the largest detection count of a frame, frames_per_chunk: 0 for the default; both size the workspace.
+ */
+/* bytes of the workspace `ws` of sdfr_eval_match_scores, sdfr_eval_thresholds and sdfr_eval_pr (one buffer serves the three calls in
+ * turn) for C = ML * K combinations and S sample points; -1 on bad sizes */
+int64_t sdfr_eval_ws_bytes(int G, int NG, int C, int S, int max_nd, int frames_per_chunk);
+/* out[ooff[f] + j * ng + i] = -sqrt(dx * dx + dy * dy) (float64; squares summed in this order, one square root) of detection j and ground
+ * truth i of frame f; loc float64 [n][3], columns (0, 2) if camera_frame != 0, else (0, 1) */
+int sdfr_eval_center_dist(const double* dt_loc, int ND, const double* gt_loc, int NG, int G, const int32_t* doff, const int32_t* goff,
+                          const int64_t* ooff, int camera_frame, double* out, int64_t out_len, void* stream);
+/* pass A: the greedy matching without score threshold (highest score above min_overlap wins, the first on a tie).  out float64[ML * K][NG]:
+ * the matched detection's score at every true positive's ground truth, NaN elsewhere; every element of a frame in range is written */
+int sdfr_eval_match_scores(const void* overlaps, int ov_f32, int64_t ov_len, const int64_t* ooff, const int32_t* doff, const int32_t* goff,
+                           int G, int ND, int NG, const double* dt_score, const int8_t* ign_dt, const int8_t* ign_gt, int ML, int K,
+                           const double* min_overlap, int max_nd, void* ws, int64_t ws_bytes, double* out, void* stream);
+/* get_thresholds per combination: row c of scores (float64[ML * K][NG], NaN = no score: the output of sdfr_eval_match_scores) is
+ * compacted and sorted descending in ws, then walked against num_gt[c / K] valid ground truths (int64[ML]) with the reference's float64
+ * recall arithmetic -> thr float64[ML * K][S] (zero past the count), nthr int32[ML * K] <= S, count int32[ML * K] (scores per row; may
+ * be NULL).  One launch whatever NG is */
+int sdfr_eval_thresholds(const double* scores, int NG, const int64_t* num_gt, int ML, int K, int S, void* ws, int64_t ws_bytes, double* thr,
+                         int32_t* nthr, int32_t* count, void* stream);
+/* pass B: for every combination c and threshold t < nthr[c] the matching of every frame among the detections with score >= thr[c][t]
+ * (highest overlap wins), summed over the frames: pr float64[ML * K][S][7] = tp, fp, fn, yaw error, orientation similarity, match degree,
+ * -log(score); rows t >= nthr[c] are zero.  angular == 0: columns 3 and 4 stay zero (the yaw / alpha pointers may be NULL).  dc_off
+ * int32[ML][G + 1] into dc_boxes float64[NDC][4]: the DontCare boxes of (ml, frame) for the 2-D metric's rule (an unassigned detection
+ * whose intersection with one of them over its OWN area exceeds min_overlap is no false positive); NULL: no such rule.  Frames are summed
+ * in chunks of frames_per_chunk and the chunks in order: the same inputs give the same bits on every device */
+int sdfr_eval_pr(const void* overlaps, int ov_f32, int64_t ov_len, const int64_t* ooff, const int32_t* doff, const int32_t* goff, int G,
+                 int ND, int NG, const double* dt_score, const double* dt_yaw, const double* dt_alpha, const double* gt_yaw,
+                 const double* gt_alpha, const double* dt_bbox, const int8_t* ign_dt, const int8_t* ign_gt, const double* dc_boxes,
+                 int NDC, const int32_t* dc_off, int ML, int K, const double* min_overlap, const double* thr, const int32_t* nthr,
+                 int S, int angular, int max_nd, int frames_per_chunk, void* ws, int64_t ws_bytes, double* pr, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

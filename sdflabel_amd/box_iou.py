@@ -141,6 +141,21 @@ def _frames(kind, boxes_list, qboxes_list, criterion, camera=False, device=None)
     return [t.view(n, k) for t, n, k in zip(out.split((nb * nq).tolist()), nb.tolist(), nq.tolist())]
 
 
+@_lib.traced("packed_iou")
+def packed_iou(kind, boxes, qboxes, G, offs, total, criterion=-1, camera=False):
+    """Grouped overlaps of boxes that are packed on the device already: kind "bev" (float32 [n][5]), "3d" (float64 [n][7]) or "image"
+    (float64 [n][4]); offs = (boff int32 [G + 1], qoff int32 [G + 1], ooff int64 [G + 1]) device tensors; total = ooff[G], known to the
+    caller (no read-back).  One launch, no host synchronisation; returns the flat tensor of the groups' [n_g][k_g] blocks."""
+    if boxes.dtype != _IN[kind] or qboxes.dtype != _IN[kind] or not boxes.is_cuda or not qboxes.is_cuda:
+        raise ValueError("packed %s boxes must be %s device tensors" % (kind, _IN[kind]))
+    if boxes.dim() != 2 or qboxes.dim() != 2 or boxes.shape[1] != _COLS[kind] or qboxes.shape[1] != _COLS[kind]:
+        raise ValueError("packed %s boxes must be [n][%d]" % (kind, _COLS[kind]))
+    out = torch.empty(int(total), dtype=_OUT[kind], device=boxes.device)      # the launch writes every block
+    if G and out.numel():
+        _launch(kind, boxes.contiguous(), qboxes.contiguous(), int(G), offs, _criterion(criterion), camera, out)
+    return out
+
+
 @_lib.traced("rotate_iou")
 def rotate_iou(boxes, qboxes, criterion=-1, device=None):
     """Rotated BEV overlap [N][K] float32 of boxes [N][5] and query boxes [K][5] = [x, y, dx, dy, angle], cast to float32 as the

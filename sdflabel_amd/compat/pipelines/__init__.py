@@ -1,5 +1,5 @@
-"""`pipelines` of the reference with this directory searched first: pipelines.rotate_iou resolves here, every other pipelines module
-(detection_3d, evaluate_dump, refine_css, ...) to the reference's own pipelines/ found on sys.path.
+"""`pipelines` of the reference with this directory searched first: pipelines.rotate_iou and pipelines.detection_3d resolve here, every
+other pipelines module (constants, evaluate_dump, refine_css, ...) to the reference's own pipelines/ found on sys.path.
 
 A regular package, not a namespace portion.  `python main.py` puts the reference root ahead of every PYTHONPATH entry, and a namespace
 package's search path follows sys.path order, so the reference's numba.cuda rotate_iou.py would win.  A regular package found anywhere on

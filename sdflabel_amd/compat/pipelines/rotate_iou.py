@@ -1,7 +1,7 @@
 """pipelines/rotate_iou.py of the reference (numba.cuda + mpi4py there) on sdflabel_amd.box_iou: same names and signatures.
 
-The package next to this file (__init__.py) makes pipelines.rotate_iou resolve here and every other pipelines module to the reference's
-directory, whichever of the two comes first on sys.path.  Imports neither numba nor mpi4py; every overlap is computed on the device (no
+The package next to this file (__init__.py) makes pipelines.rotate_iou (and pipelines.detection_3d) resolve here and the other pipelines modules to the
+reference's directory, whichever of the two comes first on sys.path.  Imports neither numba nor mpi4py; every overlap is computed on the device (no
 GPU: SdfrError).
 
 Dtypes: the reference computes d3_box_overlap_kernel and image_box_overlap in the dtype of its inputs (numba).  Here they compute in

@@ -31,6 +31,7 @@ extern "C" const char* sdfr_last_error(void) { return g_err; }
 // sdfr_splat_backward_x, sdfr_pose_latent_solver)
 // 401: RANSAC pose initialisation (sdfr_ransac_ws_bytes, sdfr_ransac_sample, sdfr_ransac_pose)
 // 402: the evaluator's box overlaps (sdfr_rotate_iou, sdfr_box3d_iou, sdfr_image_box_iou)
+// 403: the evaluator's statistics (sdfr_eval_*)
 extern "C" int sdfr_version(void) { return SDFR_VERSION; }
 
 // bit 0: experiment build (SDFR_EXPERIMENT: some kernel geometry or option differs from the product's); bit 1: a timing-only ablation is
