@@ -34,12 +34,13 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 403        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 404        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
  * sdfr_mlp_forward_candidates, sdfr_candidate_band, sdfr_losses_fused, sdfr_splat_backward_x, sdfr_pose_latent_solver; 401: the RANSAC pose initialisation sdfr_ransac_*; 402: the evaluator's box overlaps sdfr_rotate_iou, sdfr_box3d_iou,
- * sdfr_image_box_iou; 403: the evaluator's statistics sdfr_eval_*).  A caller built
+ * sdfr_image_box_iou; 403: the evaluator's statistics sdfr_eval_*; 404: frame labelling, sdfr_reproject and
+ * sdfr_point_extents).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -733,6 +734,30 @@ int sdfr_eval_pr(const void* overlaps, int ov_f32, int64_t ov_len, const int64_t
                  const double* gt_alpha, const double* dt_bbox, const int8_t* ign_dt, const int8_t* ign_gt, const double* dc_boxes,
                  int NDC, const int32_t* dc_off, int ML, int K, const double* min_overlap, const double* thr, const int32_t* nthr,
                  int S, int angular, int max_nd, int frames_per_chunk, void* ws, int64_t ws_bytes, double* pr, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Frame labelling (csrc/frame.hip): the per-annotation glue of pipelines/refine_css.py:130-196 and utils/refinement.py:501-562 for a
+ * frame's annotations at once.
+ */
+/* reproject (utils/refinement.py:360-410, torch branch) of B depth crops packed one behind the other:
+ *   meta int32[B][4] = (W, H, index of the crop's first pixel in depth, colour layout: 1 = [3][H][W], 0 = [H][W][3]); the crop's colours start
+ *   at color + 3 * that index.  max_pix >= every W * H.  kinv [B][9] = inverse(K) of the crop, inverted by the caller.
+ *   Kept: the pixels with depth != 0 and, if filter != 0, some colour channel > 0, in row-major order (y outer, x inner):
+ *     points[b][s] = (kinv [x, y, 1]) * depth, colors[b][s] = the pixel's colour      ([B][cap][3] each)
+ *   cnt[b] = the TRUE number of kept pixels; beyond cap nothing is written and over[b] |= over_bit (sticky; over may be NULL).
+ *   scratch: int32[B * ceil(max_pix / 256)]. */
+int sdfr_reproject(const float* depth, const float* color, const int32_t* meta, const float* kinv, int B, int max_pix, int filter, int cap,
+                   float* points, float* colors, int32_t* cnt, int32_t* scratch, int32_t* over, int over_bit, void* stream);
+/* Segmented extents: for list b < B of n_b points, p' = A_b (s_b p) + t_b in float32 (each product and sum rounded separately),
+ *   ext[b][0..6)  = min x, max x, min y, max y, min z, max z of p'
+ *   ext[b][6..10) = min u, max u, min v, max v of u = fx x'/z' + cx, v = fy y'/z' + cy (K_b [9], no distortion); NaN when K == NULL
+ *   n_out[b] = n_b; an empty list reports NaN extents.
+ * List b starts at pts + 3 * off[b] (off int64[B]) and holds cnt[b] points, or (off == NULL) is row b of a [B][cap][3] array holding
+ * min(cnt[b], cap) points (cnt == NULL: cap).  With off given, cap bounds every count.  A [B][9], scale [B], t [B][3], K [B][9]: each may be
+ * NULL (identity, 1, 0, no projection).  flags & 1: the points and the scale are float16 values and s p is rounded to float16
+ * (a float16 cloud times a float16 scale, utils/refinement.py:541). */
+int sdfr_point_extents(const float* pts, const int64_t* off, const int32_t* cnt, int cap, int B, const float* A, const float* scale,
+                       const float* t, const float* K, int flags, float* ext, int32_t* n_out, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */
