@@ -34,13 +34,13 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 404        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 405        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
  * sdfr_mlp_forward_candidates, sdfr_candidate_band, sdfr_losses_fused, sdfr_splat_backward_x, sdfr_pose_latent_solver; 401: the RANSAC pose initialisation sdfr_ransac_*; 402: the evaluator's box overlaps sdfr_rotate_iou, sdfr_box3d_iou,
  * sdfr_image_box_iou; 403: the evaluator's statistics sdfr_eval_*; 404: frame labelling, sdfr_reproject and
- * sdfr_point_extents).  A caller built
+ * sdfr_point_extents; 405: frame ingest, sdfr_depth_map, sdfr_match_boxes and sdfr_css_input).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -758,6 +758,35 @@ int sdfr_reproject(const float* depth, const float* color, const int32_t* meta, 
  * (a float16 cloud times a float16 scale, utils/refinement.py:541). */
 int sdfr_point_extents(const float* pts, const int64_t* off, const int32_t* cnt, int cap, int B, const float* A, const float* scale,
                        const float* t, const float* K, int flags, float* ext, int32_t* n_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Frame ingest (csrc/ingest.hip): what pipelines/refine_css.py:101-138 does on the host before a crop exists.
+ */
+/* compute_depth_map (utils/refinement.py:87-105).  lidar [N][3] in the camera frame, device memory, float64 (lidar_f64 != 0) or float32.
+ *   planes: HOST float[4][3], the rows of build_view_frustum(K, 0, 0, w, h); cam: HOST double[4] = fx, fy, cx, cy.  Both are read at the call.
+ *   A point is kept when all four plane . p > 0 (float64); its pixel is x = (int)(float)(fx (X / Z) + cx), y likewise (float64 pinhole
+ *   rounded to float32, truncated toward zero).  A kept point outside [0, w) x [0, h) is dropped and counted.
+ *   winner int32[h][w] = the largest index of the kept points on the pixel, -1 without one (an integer atomic maximum: the LAST point in
+ *   input order wins, as the reference's loop overwrites); depth float[h][w] = (float)Z of the winner, 0 without one.
+ *   info int32[2] = { points that landed on a pixel, kept points dropped for lying outside the image }.  Three launches. */
+int sdfr_depth_map(const void* lidar, int lidar_f64, int N, const float* planes, const double* cam, int w, int h, float* depth,
+                   int32_t* winner, int32_t* info, void* stream);
+/* The box matching of refine_css.py:101-114: anno double[A][4], det double[M][4] as [x1, y1, x2, y2].  Per annotation a:
+ *   iou[a] = the largest get_iou(det[m], anno[a]) (utils/refinement.py:128-165: 0 when width < 0 or height < 0, divisor + 1e-5), float64;
+ *   best[a] = the FIRST m that attains it (np.argmax), -1 when M == 0; keep[a] = (iou[a] >= 0.5).  One launch. */
+int sdfr_match_boxes(const double* anno, int A, const double* det, int M, int32_t* best, double* iou, int32_t* keep, void* stream);
+/* transform_bgr_crop (utils/refinement.py:60-84) for A boxes of one frame image [H][W][3] (float32 BGR, 0 ... 1, device memory).
+ *   meta int32[A][8] = { l, t, crop width, crop height, index of the crop's first mask element in masks or -1, first row of the crop in
+ *   tmp, first workgroup of the crop in the horizontal pass, 0 }: rows are counted one crop behind the other (sum of the heights so far),
+ *   workgroups likewise with ceil(height / 8) per crop; n_hblocks is their total.  Boxes must lie inside the image.
+ *   masks: float [height][width] per masked crop, multiplied into the crop in float32 first (refine_css.py:135); may be NULL.
+ *   Per pixel: uint8(trunc(v * 255.0f)), BGR -> RGB, Pillow's 8-bit bilinear resample to 128 x 128 (horizontal pass over all rows, vertical
+ *   pass over its uint8 result, coefficients in double rounded to 22-bit integers), then
+ *     im_orig [A][3][128][128] = float(u8) / 255.0f          im [A][3][128][128] = (im_orig - mean) / std      u8 [A][128][128][3]
+ *   each of the three may be NULL.  ksize >= 2 * ceil(max(largest crop extent / 128, 1)) + 1 (Pillow's ksize).
+ *   Workspaces: coef int32[A][2][128][2 + ksize], tmp uint8[total rows][128][3].  Three launches. */
+int sdfr_css_input(const float* image, int H, int W, const int32_t* meta, int A, const float* masks, int ksize, int n_hblocks,
+                   int32_t* coef, uint8_t* tmp, float* im, float* im_orig, uint8_t* u8, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

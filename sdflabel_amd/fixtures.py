@@ -107,3 +107,63 @@ def kitti_like_problems(decoder32, density, area, n, device, seed=11):
         starts.append({"yaw": y0.copy(), "trans": (gts[b] + (t0_ - np.asarray(GT_TRANS, np.float32))).astype(np.float32),
                        "scale": np.array([GT_SCALE], np.float32), "latent": l0.copy()})
     return shapes, Ks, targets, lidars, starts
+
+
+def synthetic_sample(decoder32, density, area, device, candidates=16, f0=200.0, margin=8, seed=11):
+    """A KITTI-like sample dict for pipelines.frame.refine_sample from `kitti_like_problems`: one camera of focal length f0 for the frame;
+    every chosen problem gets the box whose corner-shifted intrinsics are its own crop intrinsics scaled to f0, so its lidar-like cloud (already
+    in camera coordinates) projects into that box.  Candidates whose boxes would overlap an earlier one in x are left out.  The frame image is
+    black except inside the boxes, where it carries the problem's target NOCS image (nearest-neighbour resized, stored BGR): `StandInCSS`
+    reads it back, which stands in for a trained CSS network.
+    Returns (sample, lidar): sample = {'image' (H, W, 3) float32, 'orig_cam' 3x3 float32, 'world_to_cam' 4x4, 'annos' {'easy', 'medium',
+    'hard'}, 'gt'}, without 'depth' (build it with frame.depth_map from lidar, float64 [N][3]).  GPU only."""
+    import torch
+    import torch.nn.functional as F
+    shapes, Ks, targets, lidars, starts = kitti_like_problems(decoder32, density, area, candidates, device, seed)
+    raw, taken = [], []
+    for b in range(candidates):
+        r = f0 / float(Ks[b][0, 0])
+        Hc, Wc = int(round(shapes[b][0] * r)), int(round(shapes[b][1] * r))
+        l, t = int(round(-float(Ks[b][0, 2]) * r)), int(round(-float(Ks[b][1, 2]) * r))
+        if all(l + Wc + margin <= raw[c][0] or raw[c][0] + raw[c][2] + margin <= l for c in taken):
+            taken.append(len(raw))
+        raw.append((l, t, Wc, Hc))
+    cx0 = margin - min(raw[b][0] for b in taken)
+    cy0 = margin - min(raw[b][1] for b in taken)
+    W = max(raw[b][0] + raw[b][2] for b in taken) + cx0 + margin
+    H = max(raw[b][1] + raw[b][3] for b in taken) + cy0 + margin
+    image = np.zeros((H, W, 3), np.float32)
+    annos = []
+    for b in taken:
+        l, t, Wc, Hc = raw[b][0] + cx0, raw[b][1] + cy0, raw[b][2], raw[b][3]
+        nocs = F.interpolate(targets[b][None].float(), size=(Hc, Wc), mode="nearest")[0].permute(1, 2, 0).numpy()
+        image[t:t + Hc, l:l + Wc] = nocs[:, :, ::-1]
+        centre = lidars[b].mean(0).astype(np.float64)
+        annos.append({"name": "Car", "bbox": np.array([l, t, l + Wc, t + Hc]), "location": centre + [0.0, 0.8, 0.0],
+                      "dimensions": np.array([1.6, 1.7, 3.9]), "rotation_y": float(GT_YAW), "alpha": float(GT_YAW), "occluded": 0, "truncated": 0.0,
+                      "score": 1.0, "problem": b})
+    p_WC = np.eye(4)
+    p_WC[:3, 3] = [0.1, -0.2, 0.3]
+    sample = {"image": image, "orig_cam": np.array([[f0, 0, cx0], [0, f0, cy0], [0, 0, 1]], np.float32), "world_to_cam": p_WC,
+              "annos": {"easy": annos, "medium": [], "hard": []}, "gt": annos}
+    return sample, np.concatenate([lidars[b] for b in taken]).astype(np.float64)
+
+
+def stand_in_css(latent=GT_LATENT):
+    """A small deterministic torch.nn.Module in the place of the CSS network for `synthetic_sample`: it undoes Normalize on its [n][3][128][128]
+    input, returns the image (background suppressed) times 255 as 'uvw_sm_masked' and a latent near `latent` that depends on the crop."""
+    import torch
+
+    class StandInCSS(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.register_buffer("mean", torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1))
+            self.register_buffer("std", torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1))
+            self.register_buffer("base", torch.tensor(list(latent), dtype=torch.float32))
+
+        def forward(self, x):
+            rgb = (x * self.std + self.mean).clamp(0, 1)
+            fg = (rgb.amax(1, keepdim=True) > 0.1).to(x.dtype)
+            return {"uvw_sm_masked": rgb * fg * 255, "latent": self.base + 0.05 * torch.tanh(x.mean((2, 3)))}
+
+    return StandInCSS()

@@ -8,6 +8,13 @@ the refinement and the evaluator, for all annotations of a frame at once.
                      sdfr_point_extents, ONE device -> host copy per chunk, then the label in numpy float64 (assemble_labels)
   frame_dict         refine_css.py:242-245: a frame's labels stacked into the {key: ndarray} dict the evaluator takes
 
+and the ingest of a frame, what the reference does on the host before a crop exists (csrc/ingest.hip):
+
+  depth_map          utils/refinement.py:87-105 (compute_depth_map): the lidar rasterised into the sparse depth image -- sdfr_depth_map
+  match_boxes        refine_css.py:101-114: the detector box of the largest get_iou per annotation, kept from 0.5 -- sdfr_match_boxes
+  css_inputs_many    utils/refinement.py:60-84 (transform_bgr_crop) for all boxes of a frame, cut from the frame image on the device, Pillow's
+                     8-bit bilinear resample reproduced byte for byte -- sdfr_css_input
+
 There is no CPU fallback for the point arithmetic; the host parts (init_params_host, assemble_labels and the small helpers) are plain numpy
 and are tested without a GPU against values recorded from the reference's own functions.
 """
@@ -438,3 +445,152 @@ def surfaces_many(dsdf, grid, latents):
         sdf, _ = dsdf(torch.cat([lat.expand(pts.size(0), -1), pts], 1))
         out.append(tuple(t.detach() for t in grid.get_surface_points(sdf)))
     return out
+
+
+# ---- ingest: depth map, box matching, CSS inputs ----------------------------------------------------------------------------------------
+CSS_SIZE = 128                                                                          # transforms.Resize((128, 128)), utils/refinement.py:74
+
+
+def _host_array(a, dtype=None):
+    a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    return a if dtype is None else a.astype(dtype, copy=False)
+
+
+def _device_rows(a, width, device):
+    """[n][width] on the device (an empty input is made there: there is nothing to copy)"""
+    n = a.numel() if torch.is_tensor(a) else np.asarray(a).size
+    if n == 0:
+        return torch.zeros((0, width), dtype=torch.float64, device=device)
+    return _as_tensor(a, device).reshape(-1, width)
+
+
+def unproject(K, p2d):
+    """utils/refinement.py:475-477: the rays ((u - cx) / fx, (v - cy) / fy, 1) through pixels p2d [n][2], float32.  cv2.undistortPoints without
+    distortion is taken to be this pinhole (evaluated in float64, as cv2 does internally, and rounded to float32); cv2 is not installed where
+    this was developed, so that equivalence is not tested."""
+    K = _host_array(K, np.float64)
+    p = np.asarray(p2d, np.float64).reshape(-1, 2)
+    return np.stack([(p[:, 0] - K[0, 2]) / K[0, 0], (p[:, 1] - K[1, 2]) / K[1, 1], np.ones(len(p))], 1).astype(np.float32)
+
+
+def build_view_frustum(K, l, t, r, b):
+    """utils/refinement.py:480-494: the four inward plane normals (top, right, bottom, left) of the frustum through the box's corner pixels,
+    float32 [4][3]"""
+    corners = np.asarray([(l, t), (r - 1, t), (r - 1, b - 1), (l, b - 1)], dtype=np.float32)
+    rays = unproject(K, corners)
+    rays /= np.linalg.norm(rays, axis=1)[:, None]
+    return np.stack((np.cross(rays[0], rays[1]), np.cross(rays[1], rays[2]), np.cross(rays[2], rays[3]), np.cross(rays[3], rays[0])))
+
+
+def build_cam_frustum(K, img_w, img_h):
+    """utils/refinement.py:497-498"""
+    return build_view_frustum(K, 0, 0, img_w, img_h)
+
+
+@_lib.traced("depth_map")
+def depth_map(lidar, K, w, h, return_info=False):
+    """compute_depth_map (utils/refinement.py:87-105) on the device: the lidar points [N][3] (camera frame; float64 or float32, host or
+    device) inside the view frustum of the w x h image, projected by the pinhole of K in float64, rounded to float32 and truncated to a
+    pixel.  Where several points land on a pixel the LAST one in input order sets it, as the reference's loop overwrites -- by an integer
+    atomic maximum of the point index, so two runs give the same image.  The frustum planes are computed on the host (build_view_frustum).
+    A kept point that float32 rounding puts at x == w or y == h (the reference raises IndexError there) is dropped and counted.
+    `project` = cv2.projectPoints is taken to be the plain pinhole, as in init_params_many.
+    No host synchronisation.  Returns depth float32 [h][w] on the device; with return_info also {'winner': int32 [h][w] (the index of the
+    point behind each pixel, -1 without one), 'counts': int32 [2] = (points that landed on a pixel, points dropped outside the image)}."""
+    w, h = int(w), int(h)
+    dev = _device(lidar)
+    if dev.type != "cuda":
+        raise _lib.SdfrError("depth_map runs on the GPU only; there is no CPU fallback")
+    Kh = _host_array(K, np.float64).reshape(3, 3)
+    planes = np.ascontiguousarray(build_view_frustum(Kh, 0, 0, w, h), dtype=np.float32)
+    cam = np.array([Kh[0, 0], Kh[1, 1], Kh[0, 2], Kh[1, 2]], np.float64)
+    pts = _device_rows(lidar, 3, dev)
+    if pts.dtype not in (torch.float32, torch.float64):
+        pts = pts.double()
+    pts = pts.contiguous()
+    depth = torch.empty((h, w), dtype=torch.float32, device=dev)
+    winner = torch.empty((h, w), dtype=torch.int32, device=dev)
+    counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    with _lib.guard(dev):
+        ck(_lib.lib().sdfr_depth_map(P(pts), int(pts.dtype == torch.float64), int(pts.shape[0]), planes.ctypes.data, cam.ctypes.data, w, h,
+                                     P(depth), P(winner), P(counts), _lib.stream_ptr()), "sdfr_depth_map")
+    return (depth, {"winner": winner, "counts": counts}) if return_info else depth
+
+
+@_lib.traced("match_boxes")
+def match_boxes(anno_boxes, det_boxes):
+    """The matching of refine_css.py:101-114 for A annotation boxes against M detector boxes ([x1, y1, x2, y2] rows, host or device): get_iou
+    (utils/refinement.py:128-165) in float64 -- the boxes are widened to float64 first, whatever they come in --, per annotation the FIRST
+    detector box of the largest IoU (np.argmax).  No host synchronisation.
+    Returns device tensors (best int32 [A], iou float64 [A], keep bool [A] = iou >= 0.5); best is -1 where there is no detector box."""
+    dev = _device(anno_boxes, det_boxes)
+    if dev.type != "cuda":
+        raise _lib.SdfrError("match_boxes runs on the GPU only; there is no CPU fallback")
+    a = _device_rows(anno_boxes, 4, dev).double().contiguous()
+    d = _device_rows(det_boxes, 4, dev).double().contiguous()
+    A, M = int(a.shape[0]), int(d.shape[0])
+    best = torch.empty((A,), dtype=torch.int32, device=dev)
+    iou = torch.empty((A,), dtype=torch.float64, device=dev)
+    keep = torch.empty((A,), dtype=torch.int32, device=dev)
+    with _lib.guard(dev):
+        ck(_lib.lib().sdfr_match_boxes(P(a), A, P(d) if M else None, M, P(best), P(iou), P(keep), _lib.stream_ptr()), "sdfr_match_boxes")
+    return best, iou, keep.bool()
+
+
+@_lib.traced("css_inputs_many")
+def css_inputs_many(image, boxes, masks=None, orig=False, return_u8=False):
+    """transform_bgr_crop (utils/refinement.py:60-84) for all A boxes of a frame in one launch sequence, cut from the frame image on the
+    device: per crop (crop * 255).astype(uint8) in float32, BGR -> RGB, PIL's 8-bit bilinear resize to 128 x 128 (reproduced byte for byte:
+    horizontal pass over all rows, vertical pass over its uint8 result, 22-bit integer coefficients computed in double), ToTensor
+    (float32(u8) / 255) and Normalize ((x - mean) / std).
+
+    image: the frame [H][W][3], float32 BGR in 0 ... 1 (sample['image']), host or device.  boxes: A rows [l, t, r, b] of integers inside the
+    image (host values; a device tensor is fetched).  masks: None, or per box None / a [b - t][r - l] mask that is multiplied into the crop
+    in float32 first (refine_css.py:135, label_type 'maskrcnn').
+    No host synchronisation for host boxes.  Returns im float32 [A][3][128][128] on the device; with orig (im, im_orig) where im_orig is the
+    image before Normalize; with return_u8 additionally the resampled uint8 image [A][128][128][3]."""
+    dev = _device(image)
+    if dev.type != "cuda":
+        raise _lib.SdfrError("css_inputs_many runs on the GPU only; there is no CPU fallback")
+    img = _as_tensor(image, dev)
+    if img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError("css_inputs_many: the image must be (H, W, 3), got %s" % (tuple(img.shape),))
+    img = img.float().contiguous()
+    H, W = int(img.shape[0]), int(img.shape[1])
+    bx = _host_array(boxes).reshape(-1, 4)
+    if not np.array_equal(bx, np.trunc(bx)):
+        raise ValueError("css_inputs_many: boxes must hold integers (the reference slices the image with them)")
+    bx = bx.astype(np.int64)
+    A = int(bx.shape[0])
+    f32 = dict(dtype=torch.float32, device=dev)
+    im = torch.empty((A, 3, CSS_SIZE, CSS_SIZE), **f32)
+    im_orig = torch.empty((A, 3, CSS_SIZE, CSS_SIZE), **f32) if orig else None
+    u8 = torch.empty((A, CSS_SIZE, CSS_SIZE, 3), dtype=torch.uint8, device=dev) if return_u8 else None
+    if A:
+        if masks is not None and len(masks) != A:
+            raise ValueError("css_inputs_many: one mask (or None) per box")
+        meta = np.zeros((A, 8), np.int32)
+        rows = blocks = melems = 0
+        mlist = []
+        for i, (l, t, r, b) in enumerate(bx.tolist()):
+            if not (0 <= l < r <= W and 0 <= t < b <= H):
+                raise ValueError("css_inputs_many: box %d = %s is empty or outside the %d x %d image" % (i, [l, t, r, b], W, H))
+            m = None if masks is None else masks[i]
+            meta[i] = (l, t, r - l, b - t, -1 if m is None else melems, rows, blocks, 0)
+            if m is not None:
+                if tuple(m.shape) != (b - t, r - l):
+                    raise ValueError("css_inputs_many: mask %d has shape %s for a %d x %d crop" % (i, tuple(m.shape), b - t, r - l))
+                mlist.append(m.float() if torch.is_tensor(m) else np.asarray(m, np.float32))
+                melems += (b - t) * (r - l)
+            rows += b - t
+            blocks += (b - t + 7) // 8
+        ksize = 2 * int(math.ceil(max(float(meta[:, 2:4].max()) / CSS_SIZE, 1.0))) + 1
+        meta_d = _upload(torch.from_numpy(meta), dev)
+        masks_d = _pack_flat(mlist, dev) if mlist else None
+        coef = torch.empty((A, 2, CSS_SIZE, 2 + ksize), dtype=torch.int32, device=dev)
+        tmp = torch.empty((rows, CSS_SIZE, 3), dtype=torch.uint8, device=dev)
+        with _lib.guard(dev):
+            ck(_lib.lib().sdfr_css_input(P(img), H, W, P(meta_d), A, P(masks_d), ksize, blocks, P(coef), P(tmp), P(im), P(im_orig), P(u8),
+                                         _lib.stream_ptr()), "sdfr_css_input")
+    out = (im,) + ((im_orig,) if orig else ()) + ((u8,) if return_u8 else ())
+    return out[0] if len(out) == 1 else out

@@ -3,16 +3,23 @@ annotations.  It contains nothing but calls of the public stages, in the referen
 
     from sdflabel_amd.pipelines.frame import refine_frame
 
-What stays with the caller (it needs the dataset, the CSS network or Mask R-CNN): loading the frame, matching boxes, cutting the crops and
-running the CSS network on them.
+refine_frame starts from finished crops.  refine_sample starts from a loaded KITTI sample: it selects the annotations, builds the depth map
+from the lidar if asked, matches the detector's boxes, cuts the crops on the device, prepares the CSS network's input, runs the network once
+over all crops and hands the result to refine_frame.  What stays with the caller: loading the frame (datasets/kitti.py, the road-plane
+removal of get_kitti_frame) and the CSS network itself, which is any torch.nn.Module passed in.
 """
+from collections import defaultdict
+
+import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..frame import frame_dict, init_params_many, labels_many, reproject_many, surfaces_many
+from .. import _lib
+from ..frame import (NECESSARY_KEYS, _as_tensor, css_inputs_many, depth_map, frame_dict, init_params_many, labels_many, match_boxes,
+                     reproject_many, surfaces_many)
 from .optimizer import optimize_many
 from .pose import PoseEstimator
-from .refinement import adjust_intrinsics_crop
+from .refinement import adjust_intrinsics_crop, get_annos
 
 
 def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, iters, weights, pose_type='kabsch', scale=2.0, rendering_area=32,
@@ -58,3 +65,102 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
         return est, kept, {'crop_sizes': sizes, 'intrinsics': intr, 'off_intrinsics': off, 'lidar': lidar, 'nocs_3d': nocs3d, 'surfaces': surf,
                            'poses': poses, 'params': refined, 'labels': labels}
     return est, kept
+
+
+def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_annos='', label_type='gt', maskrcnn_labels=None, lidar=None,
+                  css_batch=None, pose_type='kabsch', scale=2.0, rendering_area=32, sampler='device', seed=0, keys=None, optimize_kwargs=None,
+                  return_stages=False):
+    """One KITTI sample from the loaded frame to the evaluator's dicts: the body of the reference's frame loop (refine_css.py:94-245).
+
+    sample: {'image' (H, W, 3) float32 BGR in 0 ... 1, 'orig_cam' 3x3, 'world_to_cam' 4x4, 'annos' {'easy', 'medium', 'hard'} and 'depth'
+    (H, W), the sparse depth map}.  With `lidar` ([N][3], camera frame, already restricted to what should be rasterised -- the reference
+    removes the road plane first) the depth map is built by frame.depth_map instead and sample['depth'] is not read.
+    css_net: a module mapping [n][3][128][128] to {'uvw_sm_masked', 'latent'}.  annos: the annotations to label; None selects them with
+    get_annos(diff_annos, sample).  label_type: 'gt' (the annotations' own boxes), 'rcnn' or 'maskrcnn' with maskrcnn_labels = {'bboxes'
+    [M][4], 'masks' per detector box a mask of its truncated box}.  The remaining arguments are refine_frame's.
+
+    Steps: (1) the annotations; (2) for 'rcnn' / 'maskrcnn' frame.match_boxes: an annotation whose best detector box has get_iou < 0.5 is
+    dropped, the others take that box truncated to integers (:101-114); (3) colour and depth crops as views of the frame on the device;
+    (4) frame.css_inputs_many -- for 'maskrcnn' with the matched mask, which goes into the CSS input only: the lidar crop's colours are
+    reprojected unmasked, as the reference masks crop_bgr after its reproject (:130-135); (5) ONE css_net forward over all crops under
+    torch.no_grad(), NOCS = uvw_sm_masked / 255 and the latent in the grid's precision (:142-144); (6) refine_frame, unchanged.
+
+    BATCHING THE CSS FORWARD may differ in low bits from the reference's batch-1 calls, because the convolution algorithm the backend
+    picks can depend on the batch size.  css_batch=1 restores one call per crop (css_batch=k: chunks of k crops).
+    The caller's sample and annotations are not modified (the reference overwrites anno['bbox'] with the matched box).
+
+    Host synchronisations beyond refine_frame's: none for 'gt'; one for 'rcnn' / 'maskrcnn', the read of the match.
+    Returns (frame_estimations, kept, frame_annos): refine_frame's dict and the indices into the selected annotations behind its rows, and
+    the {key: list / ndarray} dict of ALL selected annotations the evaluator takes as the frame's ground truth (:97, :242-245; with their
+    original boxes, and including the annotations that were dropped, as the reference appends before it skips; a key of alpha, bbox,
+    dimensions, location, rotation_y, score that no annotation carries is left out, where the reference stores an empty array).  With return_stages a
+    fourth value: refine_frame's stages (rows: the annotations that passed the matching) plus 'annos', 'boxes', 'match', 'depth', 'css_input',
+    'css_input_orig', 'nocs_pred', 'latents'.  keys, if given, holds one RANSAC key per selected annotation."""
+    if label_type not in ('gt', 'rcnn', 'maskrcnn'):
+        raise ValueError("refine_sample: label_type must be 'gt', 'rcnn' or 'maskrcnn'")
+    device = grid.points.device
+    if device.type != 'cuda':
+        raise _lib.SdfrError("refine_sample runs on the GPU only; there is no CPU fallback")
+    precision = grid.points.dtype
+    annos = get_annos(diff_annos, sample) if annos is None else list(annos)
+    frame_annos = defaultdict(list)
+    for anno in annos:
+        for key, value in anno.items():
+            frame_annos[key].append(value)
+    for key in NECESSARY_KEYS:
+        if key in frame_annos:                                                    # (the reference makes an empty array of a key no annotation has)
+            frame_annos[key] = np.asarray(frame_annos[key])
+    frame_annos = dict(frame_annos)
+    image = _as_tensor(sample['image'], device)
+    H, W = int(image.shape[0]), int(image.shape[1])
+    K_orig = sample['orig_cam']
+    depth = depth_map(lidar, K_orig, W, H) if lidar is not None else _as_tensor(sample['depth'], device)
+    # boxes
+    live = list(range(len(annos)))
+    boxes = [[int(v) for v in np.asarray(a['bbox']).tolist()] if label_type == 'gt' else None for a in annos]
+    if label_type == 'gt':
+        for a, bx in zip(annos, boxes):
+            if not np.array_equal(np.asarray(a['bbox']), np.asarray(bx)):
+                raise ValueError("refine_sample: an annotation's bbox must hold integers for label_type='gt' (the reference slices the image with it)")
+    masks, match = None, None
+    if label_type != 'gt':
+        if maskrcnn_labels is None:
+            raise ValueError("refine_sample: label_type %r needs maskrcnn_labels" % label_type)
+        det = maskrcnn_labels['bboxes']
+        det = det.detach().cpu().numpy() if torch.is_tensor(det) else np.asarray(det)
+        live, best_h = [], np.zeros(0, np.int32)
+        if annos:
+            best, iou, keep = match_boxes(np.asarray([np.asarray(a['bbox'], np.float64) for a in annos]), det)
+            host = torch.stack([best, keep.int()]).cpu().numpy()                  # the one host synchronisation of the matching
+            best_h = host[0]
+            live = [i for i in range(len(annos)) if host[1, i]]
+            match = {'best': best, 'iou': iou, 'keep': keep}
+        for i in live:
+            boxes[i] = det[best_h[i]].astype(np.int64).tolist()                    # bbox_maskrcnn.astype(np.int): truncation
+        if label_type == 'maskrcnn':
+            masks = [maskrcnn_labels['masks'][int(best_h[i])] for i in live]
+    lboxes = [boxes[i] for i in live]
+    # crops (views of the frame on the device) and the CSS network's input
+    colors = [image[t:b, l:r] for l, t, r, b in lboxes]
+    depths = [depth[t:b, l:r] for l, t, r, b in lboxes]
+    css_in, css_vis = css_inputs_many(image, np.asarray(lboxes, np.int64).reshape(-1, 4), masks=masks, orig=True)
+    nocs, latents = [], []
+    if live:
+        step = len(live) if not css_batch else max(1, int(css_batch))
+        with torch.no_grad():
+            for c0 in range(0, len(live), step):
+                pred = css_net(css_in[c0:c0 + step])
+                uvw, lat = pred['uvw_sm_masked'].detach(), pred['latent'].detach()
+                for j in range(uvw.shape[0]):
+                    nocs.append(uvw[j] / 255.)
+                    latents.append(lat[j].to(precision))
+    annotations = [{'bbox': lboxes[j], 'color': colors[j], 'depth': depths[j], 'nocs_pred': nocs[j]} for j in range(len(live))]
+    out = refine_frame(annotations, dsdf, grid, latents, K_orig, sample['world_to_cam'], iters, weights, pose_type=pose_type, scale=scale,
+                       rendering_area=rendering_area, sampler=sampler, seed=seed, keys=None if keys is None else [keys[i] for i in live],
+                       optimize_kwargs=optimize_kwargs, return_stages=return_stages)
+    kept = [live[j] for j in out[1]]
+    if return_stages:
+        stages = dict(out[2], annos=annos, boxes=boxes, match=match, css_input=css_in, css_input_orig=css_vis, nocs_pred=nocs, latents=latents,
+                      depth=depth)
+        return out[0], kept, frame_annos, stages
+    return out[0], kept, frame_annos

@@ -3,22 +3,71 @@ import line:
 
     from sdflabel_amd.pipelines import refinement as rtools      # was: import utils.refinement as rtools
 
-Ported: reproject, get_kitti_label, roty_in_bev, alpha_in_bev, compute_iou, get_iou, adjust_intrinsics_crop, rot_from_yaw -- same
-signatures, same return values.  The dataset, visualisation and cv2 helpers of that module (transform_bgr_crop, compute_depth_map, project,
-the open3d line sets, ...) are not ported, which is why there is no module of that name under compat/: it would shadow them.
+Ported: reproject, get_kitti_label, roty_in_bev, alpha_in_bev, compute_iou, get_iou, adjust_intrinsics_crop, rot_from_yaw, compute_depth_map,
+build_view_frustum, build_cam_frustum, unproject, transform_bgr_crop, get_annos, is_anno_easy / _moderate / _hard -- same signatures, same
+return values.  The remaining dataset, visualisation and cv2 helpers of that module (get_kitti_frame with its open3d road-plane removal,
+project, the open3d line sets, ...) are not ported, which is why there is no module of that name under compat/: it would shadow them.
 
 Differences from the reference, all deliberate:
   - reproject of numpy inputs runs on the device in float32 like the torch branch and returns float32 numpy arrays (the reference's numpy
     branch computes in float64; the optimiser casts that cloud to float32, optimizer.py:64); `filter` works for both kinds of input;
-  - get_kitti_label returns `scaled_points` as a numpy array, fetched from the device on return (labels_many keeps it there).
-A frame's annotations are better served by sdflabel_amd.frame (reproject_many, init_params_many, labels_many): one launch sequence and one
-synchronisation per stage instead of one per annotation.
+  - get_kitti_label returns `scaled_points` as a numpy array, fetched from the device on return (labels_many keeps it there);
+  - compute_depth_map drops a point that float32 rounding puts at x == w or y == h, where the reference raises IndexError;
+  - transform_bgr_crop needs neither cv2, PIL nor torchvision: PIL's 8-bit bilinear resize is reproduced byte for byte on the device; it
+    returns CPU tensors, as the reference does, and does not modify crop_bgr;
+  - cv2.undistortPoints / cv2.projectPoints are taken to be the plain pinhole (cv2 is not installed where this was developed: untested).
+A frame's annotations are better served by sdflabel_amd.frame (reproject_many, init_params_many, labels_many, css_inputs_many): one launch
+sequence and one synchronisation per stage instead of one per annotation; pipelines.frame.refine_sample is the whole loop for a sample.
 """
 import numpy as np
 import torch
 
-from ..frame import (adjust_intrinsics_crop, alpha_in_bev, compute_iou, get_iou, labels_many, reproject_many, rot_from_yaw,  # noqa: F401
-                     roty_in_bev)
+from ..frame import (adjust_intrinsics_crop, alpha_in_bev, build_cam_frustum, build_view_frustum, compute_iou, css_inputs_many,  # noqa: F401
+                     depth_map, get_iou, labels_many, reproject_many, rot_from_yaw, roty_in_bev, unproject)
+
+
+def is_anno_easy(anno):
+    """utils/refinement.py:15-27: KITTI difficulty "easy" -- not occluded, truncated at most 0.15, box at least 40 pixels high"""
+    height = anno['bbox'][3] - anno['bbox'][1]
+    return not ((anno['occluded'] > 0) or (anno['truncated'] > 0.15) or height < 40)
+
+
+def is_anno_moderate(anno):
+    """utils/refinement.py:30-42: "moderate" -- occluded at most 1, truncated at most 0.30, box at least 25 pixels high"""
+    height = anno['bbox'][3] - anno['bbox'][1]
+    return not ((anno['occluded'] > 1) or (anno['truncated'] > 0.30) or height < 25)
+
+
+def is_anno_hard(anno):
+    """utils/refinement.py:45-57: "hard" -- occluded at most 2, truncated at most 0.5, box at least 25 pixels high"""
+    height = anno['bbox'][3] - anno['bbox'][1]
+    return not ((anno['occluded'] > 2) or (anno['truncated'] > 0.5) or height < 25)
+
+
+def get_annos(diff_annos, sample):
+    """utils/refinement.py:565-583: the sample's annotations up to a difficulty ('hard': all three lists, 'medium': easy + medium, anything
+    else: easy), sorted by ascending depth (a stable sort, as sorted is)"""
+    if diff_annos == 'hard':
+        annos = sample['annos']['easy'] + sample['annos']['medium'] + sample['annos']['hard']
+    elif diff_annos == 'medium':
+        annos = sample['annos']['easy'] + sample['annos']['medium']
+    else:
+        annos = sample['annos']['easy']
+    return sorted(annos, key=lambda i: i['location'][2])
+
+
+def compute_depth_map(lidar, cam, w, h):
+    """utils/refinement.py:87-105: the sparse depth image (h, w) float32 of the lidar points inside the camera's frustum, as a numpy array
+    (frame.depth_map keeps it on the device)"""
+    return depth_map(lidar, cam, w, h).cpu().numpy()
+
+
+def transform_bgr_crop(crop_bgr, orig=False):
+    """utils/refinement.py:60-84: a BGR crop (H, W, 3) in 0 ... 1 as the CSS network's input, a (3, 128, 128) float32 CPU tensor (with orig:
+    and the same image before Normalize).  The one-crop call of frame.css_inputs_many."""
+    H, W = int(crop_bgr.shape[0]), int(crop_bgr.shape[1])
+    out = css_inputs_many(crop_bgr, [[0, 0, W, H]], orig=orig)
+    return (out[0][0].cpu(), out[1][0].cpu()) if orig else out[0].cpu()
 
 
 def reproject(color, depth, K, flip_color_channels=False, filter=False):
