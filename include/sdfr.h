@@ -34,13 +34,14 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 405        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 406        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
  * sdfr_mlp_forward_candidates, sdfr_candidate_band, sdfr_losses_fused, sdfr_splat_backward_x, sdfr_pose_latent_solver; 401: the RANSAC pose initialisation sdfr_ransac_*; 402: the evaluator's box overlaps sdfr_rotate_iou, sdfr_box3d_iou,
  * sdfr_image_box_iou; 403: the evaluator's statistics sdfr_eval_*; 404: frame labelling, sdfr_reproject and
- * sdfr_point_extents; 405: frame ingest, sdfr_depth_map, sdfr_match_boxes and sdfr_css_input).  A caller built
+ * sdfr_point_extents; 405: frame ingest, sdfr_depth_map, sdfr_match_boxes and sdfr_css_input; 406: the CSS output head, sdfr_css_head and
+ * sdfr_css_latent).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -787,6 +788,27 @@ int sdfr_match_boxes(const double* anno, int A, const double* det, int M, int32_
  *   Workspaces: coef int32[A][2][128][2 + ksize], tmp uint8[total rows][128][3].  Three launches. */
 int sdfr_css_input(const float* image, int H, int W, const int32_t* meta, int A, const float* masks, int ksize, int n_hblocks,
                    int32_t* coef, uint8_t* tmp, float* im, float* im_orig, uint8_t* u8, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The CSS network's output head (csrc/css_head.hip): networks/resnet_css.py:194-196 and :203-249 of the reference, inference only.
+ */
+/* Features x_u, x_v, x_w, x_mask: contiguous float32 NCHW [B][C][H][W] with C == 64 (anything else is refused).  Weights w_* [256][64] with
+ * biases b_* [256] of out_u / out_v / out_w, w_mask [2][64] with b_mask [2] of out_mask.  Per pixel, with logit = W x + b (exact-f32 MFMA,
+ * k = 0 ... 63 in order, the bias last):
+ *   uvw_sm        [B][3][H][W]  sum_k k softmax_k(100 logit) per colour head (the maximum is subtracted before exp)
+ *   mask          [B][2][H][W]  the raw mask logits
+ *   mask_sm       [B][1][H][W]  softmax(100 mask)[1]
+ *   uvw_sm_masked [B][3][H][W]  uvw_sm where mask[1] > mask[0], else 0 (a tie is background, as argmax returns the first index)
+ *   u, v, w       [B][256][H][W] log_softmax(logit); all three NULL: not computed
+ * A pixel's result does not depend on B, on its neighbours or on the launch.  B == 0 or H * W == 0: success, nothing written.  One launch
+ * on `stream`; the tensors must live on the current device. */
+int sdfr_css_head(const float* x_u, const float* x_v, const float* x_w, const float* x_mask, int B, int C, int H, int W, const float* w_u,
+                  const float* b_u, const float* w_v, const float* b_v, const float* w_w, const float* b_w, const float* w_mask,
+                  const float* b_mask, float* uvw_sm, float* uvw_sm_masked, float* mask, float* mask_sm, float* u, float* v, float* w,
+                  void* stream);
+/* out_lat on x4 [B][C][h][w] (C == 256): the 1x1 convolution w_lat [3][256], b_lat [3] per pixel, the mean over the h * w pixels, then
+ * latent[b] = v * (1 / (|v| + 1e-8)) (project_vecs_onto_sphere, radius 1).  One workgroup per crop, fixed-order sums.  latent [B][3]. */
+int sdfr_css_latent(const float* x4, int B, int C, int h, int w, const float* w_lat, const float* b_lat, float* latent, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

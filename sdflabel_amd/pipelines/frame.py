@@ -75,7 +75,8 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
     sample: {'image' (H, W, 3) float32 BGR in 0 ... 1, 'orig_cam' 3x3, 'world_to_cam' 4x4, 'annos' {'easy', 'medium', 'hard'} and 'depth'
     (H, W), the sparse depth map}.  With `lidar` ([N][3], camera frame, already restricted to what should be rasterised -- the reference
     removes the road plane first) the depth map is built by frame.depth_map instead and sample['depth'] is not read.
-    css_net: a module mapping [n][3][128][128] to {'uvw_sm_masked', 'latent'}.  annos: the annotations to label; None selects them with
+    css_net: a module mapping [n][3][128][128] to {'uvw_sm_masked', 'latent'}; the shipped one is sdflabel_amd.networks.resnet_css.setup_css
+    (the reference's network with its output head fused on the device, loads a reference css.pt).  annos: the annotations to label; None selects them with
     get_annos(diff_annos, sample).  label_type: 'gt' (the annotations' own boxes), 'rcnn' or 'maskrcnn' with maskrcnn_labels = {'bboxes'
     [M][4], 'masks' per detector box a mask of its truncated box}.  The remaining arguments are refine_frame's.
 
@@ -87,6 +88,9 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
 
     BATCHING THE CSS FORWARD may differ in low bits from the reference's batch-1 calls, because the convolution algorithm the backend
     picks can depend on the batch size.  css_batch=1 restores one call per crop (css_batch=k: chunks of k crops).
+    A network in TRAIN mode -- setup_css's default, and how refine_css.py:40 runs it -- normalises every BatchNorm layer with the statistics of
+    the batch it is given, so there a crop's prediction depends on the other crops of the call: only css_batch=1 reproduces the reference's
+    per-crop statistics.  (The fused output head itself gives a crop the same bits in any batch.)
     The caller's sample and annotations are not modified (the reference overwrites anno['bbox'] with the matched box).
 
     Host synchronisations beyond refine_frame's: none for 'gt'; one for 'rcnn' / 'maskrcnn', the read of the match.
