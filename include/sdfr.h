@@ -34,14 +34,14 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 406        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 407        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
  * sdfr_mlp_forward_candidates, sdfr_candidate_band, sdfr_losses_fused, sdfr_splat_backward_x, sdfr_pose_latent_solver; 401: the RANSAC pose initialisation sdfr_ransac_*; 402: the evaluator's box overlaps sdfr_rotate_iou, sdfr_box3d_iou,
  * sdfr_image_box_iou; 403: the evaluator's statistics sdfr_eval_*; 404: frame labelling, sdfr_reproject and
  * sdfr_point_extents; 405: frame ingest, sdfr_depth_map, sdfr_match_boxes and sdfr_css_input; 406: the CSS output head, sdfr_css_head and
- * sdfr_css_latent).  A caller built
+ * sdfr_css_latent; 407: its training losses and gradients, sdfr_css_head_loss and sdfr_css_latent_loss).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -809,6 +809,31 @@ int sdfr_css_head(const float* x_u, const float* x_v, const float* x_w, const fl
 /* out_lat on x4 [B][C][h][w] (C == 256): the 1x1 convolution w_lat [3][256], b_lat [3] per pixel, the mean over the h * w pixels, then
  * latent[b] = v * (1 / (|v| + 1e-8)) (project_vecs_onto_sphere, radius 1).  One workgroup per crop, fixed-order sums.  latent [B][3]. */
 int sdfr_css_latent(const float* x4, int B, int C, int h, int w, const float* w_lat, const float* b_lat, float* latent, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training the CSS head (csrc/css_train.hip): the losses of pipelines/train_css.py:71-80 of the reference and their gradients for UNIT
+ * upstream gradient.  Nothing 256 channels wide is written to global memory, no atomics: the same bits in every run.
+ */
+#define SDFR_CSS_LOSS_WS_FIXED 16045824ll   /* bytes of the head loss's workspace that do not depend on the input: the workgroups' partials */
+/* Inputs as sdfr_css_head, plus uvw_gt uint8 [B][3][H][W] and mask_gt uint8 [B][H][W] (nonzero: foreground).  With N = B H W, m = mask_gt != 0,
+ * t_h = uvw_gt[:, h] m and z_h the logits of head h:
+ *   loss[0..2] = (1/N) [ sum_{m=1} (logsumexp(z_h) - z_h[t_h]) + (N - n_fg) ln 256 ]     (CrossEntropyLoss(log_softmax(z_h) * m, t_h))
+ *   loss[3]    = 2 CrossEntropyLoss(z_mask, m)
+ *   dx_* [B][64][H][W], dw_u/v/w [256][64], db_u/v/w [256], dw_mask [2][64], db_mask [2]: the gradients of the head's own loss; dx_u/v/w are
+ *   exactly 0 at background pixels.
+ * workspace: device memory of at least SDFR_CSS_LOSS_WS_FIXED + 12 N bytes (8-byte aligned); the call fails with -1 and names the size otherwise.
+ * B == 0 or H * W == 0: success, nothing written.  Four launches on `stream`. */
+int sdfr_css_head_loss(const float* x_u, const float* x_v, const float* x_w, const float* x_mask, int B, int C, int H, int W, const float* w_u,
+                       const float* b_u, const float* w_v, const float* b_v, const float* w_w, const float* b_w, const float* w_mask,
+                       const float* b_mask, const uint8_t* uvw_gt, const uint8_t* mask_gt, float* loss, float* dx_u, float* dx_v, float* dx_w,
+                       float* dx_mask, float* dw_u, float* db_u, float* dw_v, float* db_v, float* dw_w, float* db_w, float* dw_mask,
+                       float* db_mask, void* workspace, int64_t workspace_bytes, void* stream);
+/* loss[0] = mean over B * 3 of (lat - latent_gt)^2 with lat = v / (|v| + 1e-8), v = w_lat mean_p(x4) + b_lat; the length is a constant of the
+ * backward, as in the reference (project_vecs_onto_sphere detaches it): dv = 2 (lat - gt) / (3 B) / (|v| + 1e-8), dx4[b][c][p] =
+ * (w_lat^T dv_b)[c] / (h w), dw_lat [3][256] = sum_b dv_b (x) mean_p x4_b, db_lat [3] = sum_b dv_b, crops summed in order.  latent_gt float32
+ * [B][3].  workspace: at least B * 3092 bytes of device memory (8-byte aligned).  Two launches. */
+int sdfr_css_latent_loss(const float* x4, int B, int C, int h, int w, const float* w_lat, const float* b_lat, const float* latent_gt,
+                         float* loss, float* dx4, float* dw_lat, float* db_lat, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

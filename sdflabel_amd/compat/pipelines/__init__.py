@@ -1,4 +1,4 @@
-"""`pipelines` of the reference with this directory searched first: pipelines.rotate_iou and pipelines.detection_3d resolve here, every
+"""`pipelines` of the reference with this directory searched first: pipelines.rotate_iou, pipelines.detection_3d and pipelines.train_css resolve here, every
 other pipelines module (constants, evaluate_dump, refine_css, ...) to the reference's own pipelines/ found on sys.path.
 
 A regular package, not a namespace portion.  `python main.py` puts the reference root ahead of every PYTHONPATH entry, and a namespace

@@ -5,8 +5,11 @@ The convolutional body is plain torch layers (MIOpen on the GPU) under exactly t
 forward() hands the five head inputs to sdflabel_amd.css.css_head / css_latent (csrc/css_head.hip), which produce the reference's output
 dict without writing anything 256 channels wide.  The out_u / out_v / out_w / out_mask / out_lat modules only hold the parameters.
 
-INFERENCE ONLY: forward() returns detached tensors.  Train with the reference (pipelines/train_css.py is out of scope) and load the result.
-features() is torch only and runs wherever torch runs; forward() needs the GPU (no CPU fallback)."""
+forward() is the inference path and returns detached tensors.  loss() is the training path: features() with gradients, then
+sdflabel_amd.css.css_head_loss / css_latent_loss (csrc/css_train.hip), which return the losses of the reference's pipelines/train_css.py and
+hand torch's autograd the gradients of the five head inputs and the ten head parameters from one fused call each; the convolutional body
+trains through torch's own autograd.  sdflabel_amd.pipelines.train_css runs the loop and saves css.pt under the reference's names.
+features() is torch only and runs wherever torch runs; forward() and loss() need the GPU (no CPU fallback)."""
 import torch
 import torch.nn as nn
 
@@ -148,6 +151,19 @@ class ResNet(nn.Module):
         out = css.css_head(c(f['x_u']), c(f['x_v']), c(f['x_w']), c(f['x_mask']), self.head_weights(), logprobs=self.logprobs)
         out['latent'] = css.css_latent(c(f['x4']), self.out_lat.conv.weight, self.out_lat.conv.bias)
         return out
+
+
+    def loss(self, rgb, uvw_gt, mask_gt, latent_gt):
+        """The training losses of the reference (pipelines/train_css.py:65-80) for images rgb [B][3][H][W], uvw_gt [B][3][H][W] and mask_gt
+        [B][H][W] (uint8 or int64) and latent_gt [B][3]: {'loss': uvw + latent + mask, 'uvw': loss_u + loss_v + loss_w, 'mask': 2 CE,
+        'latent': MSE}, scalar tensors with gradients towards every trainable parameter.  Nothing [B][256][H][W] is formed."""
+        from .. import css
+        f = self.features(rgb)
+        c = lambda t: t.float().contiguous()              # noqa: E731
+        lh = css.css_head_loss(c(f['x_u']), c(f['x_v']), c(f['x_w']), c(f['x_mask']), self.head_weights(), uvw_gt, mask_gt)
+        latent = css.css_latent_loss(c(f['x4']), self.out_lat.conv.weight, self.out_lat.conv.bias, latent_gt.float().contiguous())
+        uvw = lh['u'] + lh['v'] + lh['w']
+        return {'loss': uvw + latent + lh['mask'], 'uvw': uvw, 'mask': lh['mask'], 'latent': latent}
 
 
 def resnet18(pretrained=False, **kwargs):
