@@ -34,14 +34,15 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 407        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 408        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
  * sdfr_mlp_forward_candidates, sdfr_candidate_band, sdfr_losses_fused, sdfr_splat_backward_x, sdfr_pose_latent_solver; 401: the RANSAC pose initialisation sdfr_ransac_*; 402: the evaluator's box overlaps sdfr_rotate_iou, sdfr_box3d_iou,
  * sdfr_image_box_iou; 403: the evaluator's statistics sdfr_eval_*; 404: frame labelling, sdfr_reproject and
  * sdfr_point_extents; 405: frame ingest, sdfr_depth_map, sdfr_match_boxes and sdfr_css_input; 406: the CSS output head, sdfr_css_head and
- * sdfr_css_latent; 407: its training losses and gradients, sdfr_css_head_loss and sdfr_css_latent_loss).  A caller built
+ * sdfr_css_latent; 407: its training losses and gradients, sdfr_css_head_loss and sdfr_css_latent_loss; 408: the road-plane removal, sdfr_lidar_normals_ws_bytes,
+ * sdfr_lidar_normals and sdfr_depth_map_masked).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -772,6 +773,11 @@ int sdfr_point_extents(const float* pts, const int64_t* off, const int32_t* cnt,
  *   info int32[2] = { points that landed on a pixel, kept points dropped for lying outside the image }.  Three launches. */
 int sdfr_depth_map(const void* lidar, int lidar_f64, int N, const float* planes, const double* cam, int w, int h, float* depth,
                    int32_t* winner, int32_t* info, void* stream);
+/* sdfr_depth_map over the points with mask[i] != 0 (uint8 [N], device memory): the depth map of the cloud without the others.  winner holds
+ * indices into the WHOLE cloud and the last kept point in input order wins, so the image equals sdfr_depth_map of the compacted cloud.
+ * This is how get_kitti_frame's road-removed map is rasterised without a compaction (and without a host synchronisation).  Three launches. */
+int sdfr_depth_map_masked(const void* lidar, int lidar_f64, int N, const uint8_t* mask, const float* planes, const double* cam, int w, int h,
+                          float* depth, int32_t* winner, int32_t* info, void* stream);
 /* The box matching of refine_css.py:101-114: anno double[A][4], det double[M][4] as [x1, y1, x2, y2].  Per annotation a:
  *   iou[a] = the largest get_iou(det[m], anno[a]) (utils/refinement.py:128-165: 0 when width < 0 or height < 0, divisor + 1e-5), float64;
  *   best[a] = the FIRST m that attains it (np.argmax), -1 when M == 0; keep[a] = (iou[a] >= 0.5).  One launch. */
@@ -788,6 +794,29 @@ int sdfr_match_boxes(const double* anno, int A, const double* det, int M, int32_
  *   Workspaces: coef int32[A][2][128][2 + ksize], tmp uint8[total rows][128][3].  Three launches. */
 int sdfr_css_input(const float* image, int H, int W, const int32_t* meta, int A, const float* masks, int ksize, int n_hblocks,
                    int32_t* coef, uint8_t* tmp, float* im, float* im_orig, uint8_t* u8, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Lidar normals (csrc/normals.hip): the normal estimation behind get_kitti_frame's road-plane removal (utils/refinement.py:628-644).
+ * The semantics are this library's own, written from Open3D's EstimateNormals / KDTreeFlann::SearchHybrid; Open3D is not installed where
+ * this was developed, so parity with it is NOT tested.
+ */
+/* points [N][3] in the camera frame, device memory, float64 (points_f64 != 0) or float32 (widened first).  planes: HOST float[4][3], the rows
+ * of build_view_frustum(K, 0, 0, W, H), read at the call; NULL: every point is in the frustum.
+ *   in_frustum uint8[N]: all four planes . p > 0 (float32 planes, float64 products, as sdfr_depth_map).  Only frustum points are queries and
+ *     only frustum points can be neighbours.
+ *   neighbours of i: the frustum points j (i itself included) with d2 = (dx*dx + dy*dy) + dz*dz < radius*radius, strictly, in float64 (the
+ *     radius is a float32 value, widened: 1.0 and 0.5 are exact);
+ *     ordered by (d2, j) ascending, the first max_nn (1 ... 64) kept -- a tie at the cut goes to the lower index.  No cap on candidates.
+ *   nn_count int32[N]; nn_idx int32[N][max_nn] in that order, padded with -1 (NULL: not written).
+ *   normals double[N][3]: with fewer than 3 neighbours (0, 0, 1); else mean and centred covariance C = (1 / k) sum (q - m)(q - m)^T in float64,
+ *     summed in neighbour order, and the unit eigenvector of C's smallest eigenvalue (cyclic Jacobi); C == 0: (0, 0, 1).  Sign: n . p <= 0
+ *     (towards the camera); a product of exactly 0 keeps the solver's sign.  Outside the frustum: (0, 0, 1), count 0.
+ * The same bits on every run; a point's result does not depend on its place in the array apart from the tie rule; no float atomic.
+ * workspace: sdfr_lidar_normals_ws_bytes(N) bytes of device memory, 16-byte aligned (-1: N out of range; N <= 2^28).  N == 0: success,
+ * nothing written.  Five launches, no host synchronisation. */
+int64_t sdfr_lidar_normals_ws_bytes(int N);
+int sdfr_lidar_normals(const void* points, int points_f64, int N, const float* planes, float radius, int max_nn, double* normals,
+                       int32_t* nn_count, int32_t* nn_idx, uint8_t* in_frustum, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The CSS network's output head (csrc/css_head.hip): networks/resnet_css.py:194-196 and :203-249 of the reference, inference only.

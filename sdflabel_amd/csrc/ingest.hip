@@ -4,6 +4,7 @@
 // sdfr_depth_map   utils/refinement.py:87-105 (compute_depth_map): frustum test, pinhole projection, truncation to a pixel, and the loop's
 //                  overwrite rule -- the LAST point in input order that lands on a pixel sets its depth.  Pass A is an integer atomicMax of
 //                  the point index, pass B a gather, so the image does not depend on scheduling and no float atomic exists.
+//                  sdfr_depth_map_masked: the same over the points a uint8 mask keeps (the road-removed map of get_kitti_frame).
 // sdfr_match_boxes refine_css.py:101-114: get_iou (utils/refinement.py:128-165) of every detector box against every annotation in float64,
 //                  the first maximum per annotation (np.argmax), kept when iou >= 0.5.
 // sdfr_css_input   utils/refinement.py:60-84 (transform_bgr_crop) for all annotations of a frame, reading the frame image in place:
@@ -25,11 +26,11 @@ __global__ __launch_bounds__(256) void sdfr_dm_init_kernel(int32_t* __restrict__
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void sdfr_dm_scatter_kernel(const T* __restrict__ lidar, int N, DmCam cam, int w, int h,
-                                                             int32_t* __restrict__ winner, int32_t* __restrict__ info) {
+__global__ __launch_bounds__(256) void sdfr_dm_scatter_kernel(const T* __restrict__ lidar, const uint8_t* __restrict__ mask, int N, DmCam cam,
+                                                             int w, int h, int32_t* __restrict__ winner, int32_t* __restrict__ info) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     bool kept = false, dropped = false;
-    if (i < N) {
+    if (i < N && (!mask || mask[i])) {                                  // a masked-out point is as good as absent from the cloud
         const double X = (double)lidar[3 * (int64_t)i], Y = (double)lidar[3 * (int64_t)i + 1], Z = (double)lidar[3 * (int64_t)i + 2];
         bool in = true;
 #pragma unroll
@@ -64,8 +65,8 @@ __global__ __launch_bounds__(256) void sdfr_dm_gather_kernel(const T* __restrict
     depth[p] = i >= 0 ? (float)lidar[3 * (int64_t)i + 2] : 0.f;
 }
 
-extern "C" int sdfr_depth_map(const void* lidar, int lidar_f64, int N, const float* planes, const double* cam, int w, int h, float* depth,
-                              int32_t* winner, int32_t* info, void* stream) {
+static int dm_run(const void* lidar, int lidar_f64, int N, const uint8_t* mask, const float* planes, const double* cam, int w, int h, float* depth,
+                  int32_t* winner, int32_t* info, void* stream) {
     SDFR_REQUIRE(N >= 0 && w > 0 && h > 0, "sdfr_depth_map: bad size");
     SDFR_REQUIRE((int64_t)w * h < ((int64_t)1 << 31), "sdfr_depth_map: image too large");
     SDFR_REQUIRE(planes && cam && depth && winner && info, "sdfr_depth_map: NULL argument");
@@ -79,9 +80,9 @@ extern "C" int sdfr_depth_map(const void* lidar, int lidar_f64, int N, const flo
     SDFR_LAUNCH_CHECK();
     if (N > 0) {
         if (lidar_f64)
-            hipLaunchKernelGGL(sdfr_dm_scatter_kernel<double>, dim3(sdfr_cdiv(N, 256)), dim3(256), 0, s, (const double*)lidar, N, c, w, h, winner, info);
+            hipLaunchKernelGGL(sdfr_dm_scatter_kernel<double>, dim3(sdfr_cdiv(N, 256)), dim3(256), 0, s, (const double*)lidar, mask, N, c, w, h, winner, info);
         else
-            hipLaunchKernelGGL(sdfr_dm_scatter_kernel<float>, dim3(sdfr_cdiv(N, 256)), dim3(256), 0, s, (const float*)lidar, N, c, w, h, winner, info);
+            hipLaunchKernelGGL(sdfr_dm_scatter_kernel<float>, dim3(sdfr_cdiv(N, 256)), dim3(256), 0, s, (const float*)lidar, mask, N, c, w, h, winner, info);
         SDFR_LAUNCH_CHECK();
     }
     if (lidar_f64)
@@ -90,6 +91,18 @@ extern "C" int sdfr_depth_map(const void* lidar, int lidar_f64, int N, const flo
         hipLaunchKernelGGL(sdfr_dm_gather_kernel<float>, dim3(sdfr_cdiv(npix, 256)), dim3(256), 0, s, (const float*)lidar, winner, npix, depth);
     SDFR_LAUNCH_CHECK();
     return SDFR_OK;
+}
+
+extern "C" int sdfr_depth_map(const void* lidar, int lidar_f64, int N, const float* planes, const double* cam, int w, int h, float* depth,
+                              int32_t* winner, int32_t* info, void* stream) {
+    return dm_run(lidar, lidar_f64, N, nullptr, planes, cam, w, h, depth, winner, info, stream);
+}
+
+// the depth map of the points with mask[i] != 0, indices and overwrite order those of the whole cloud (get_kitti_frame's road-removed map)
+extern "C" int sdfr_depth_map_masked(const void* lidar, int lidar_f64, int N, const uint8_t* mask, const float* planes, const double* cam, int w,
+                                     int h, float* depth, int32_t* winner, int32_t* info, void* stream) {
+    SDFR_REQUIRE(mask || N <= 0, "sdfr_depth_map_masked: NULL mask");
+    return dm_run(lidar, lidar_f64, N, mask, planes, cam, w, h, depth, winner, info, stream);
 }
 
 // ---- box matching ------------------------------------------------------------------------------------------------------------------------

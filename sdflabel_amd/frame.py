@@ -15,6 +15,14 @@ and the ingest of a frame, what the reference does on the host before a crop exi
   css_inputs_many    utils/refinement.py:60-84 (transform_bgr_crop) for all boxes of a frame, cut from the frame image on the device, Pillow's
                      8-bit bilinear resample reproduced byte for byte -- sdfr_css_input
 
+and the road-plane removal of the reference's get_kitti_frame (utils/refinement.py:612-656; csrc/normals.hip):
+
+  lidar_normals      a normal per lidar point from its max_nn nearest neighbours within a radius -- sdfr_lidar_normals.  The semantics are
+                     written from Open3D's estimate_normals(KDTreeSearchParamHybrid); Open3D is not installed where this was developed, so
+                     parity with it is NOT tested (tests pin a float64 restatement of the semantics instead)
+  remove_road        the points to keep: inside the frustum and |n_y| <= 0.9
+  kitti_frame        the road-removed depth map (sdfr_depth_map_masked) and the coloured scene points reprojected from it
+
 There is no CPU fallback for the point arithmetic; the host parts (init_params_host, assemble_labels and the small helpers) are plain numpy
 and are tested without a GPU against values recorded from the reference's own functions.
 """
@@ -594,3 +602,127 @@ def css_inputs_many(image, boxes, masks=None, orig=False, return_u8=False):
                                          _lib.stream_ptr()), "sdfr_css_input")
     out = (im,) + ((im_orig,) if orig else ()) + ((u8,) if return_u8 else ())
     return out[0] if len(out) == 1 else out
+
+
+# ---- road-plane removal: lidar normals, the kept points, the frame's depth map and scene cloud -------------------------------------------
+
+def _cloud(lidar, dev):
+    pts = _device_rows(lidar, 3, dev)
+    if pts.dtype not in (torch.float32, torch.float64):
+        pts = pts.double()
+    return pts.contiguous()
+
+
+def _frustum(K, w, h):
+    Kh = _host_array(K, np.float64).reshape(3, 3)
+    return Kh, np.ascontiguousarray(build_view_frustum(Kh, 0, 0, int(w), int(h)), dtype=np.float32)
+
+
+def _normals(pts, planes, radius, max_nn, want_idx):
+    dev, N, max_nn = pts.device, int(pts.shape[0]), int(max_nn)
+    if not 1 <= max_nn <= 64:
+        raise ValueError("lidar_normals: max_nn must be 1 ... 64")
+    if not (float(radius) > 0 and math.isfinite(float(radius))):
+        raise ValueError("lidar_normals: the radius must be positive and finite")
+    L = _lib.lib()
+    normals = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    cnt = torch.empty((N,), dtype=torch.int32, device=dev)
+    idx = torch.empty((N, max_nn), dtype=torch.int32, device=dev) if want_idx else None
+    inside = torch.empty((N,), dtype=torch.uint8, device=dev)
+    nbytes = int(L.sdfr_lidar_normals_ws_bytes(N))
+    if nbytes < 0:
+        raise _lib.SdfrError("lidar_normals: %d points are more than the library takes" % N)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    with _lib.guard(dev):
+        ck(L.sdfr_lidar_normals(P(pts), int(pts.dtype == torch.float64), N, None if planes is None else planes.ctypes.data, float(radius), max_nn,
+                                P(normals), P(cnt), P(idx), P(inside), P(ws), nbytes, _lib.stream_ptr()), "sdfr_lidar_normals")
+    return normals, cnt, idx, inside
+
+
+def _road_keep(pts, planes, radius, max_nn, cos_thresh):
+    """(keep bool [N], info) of remove_road for a device cloud and host frustum planes"""
+    normals, cnt, _, inside = _normals(pts, planes, radius, max_nn, False)
+    inside = inside.bool()
+    return inside & ~(normals[:, 1].abs() > float(cos_thresh)), {"normals": normals, "nn_count": cnt, "in_frustum": inside}
+
+
+@_lib.traced("lidar_normals")
+def lidar_normals(lidar, K=None, w=None, h=None, radius=1.0, max_nn=30, return_info=False):
+    """A normal per lidar point, what get_kitti_frame asks of Open3D's estimate_normals(KDTreeSearchParamHybrid(radius=1.0, max_nn=30))
+    (utils/refinement.py:628-631), on the device.  THE SEMANTICS ARE OURS, written from Open3D's EstimateNormals / KDTreeFlann::SearchHybrid;
+    Open3D is not installed where this was developed, so parity with it is NOT tested.  The tests pin a float64 restatement of these rules:
+
+    lidar [N][3], camera frame, float64 or float32 (widened first), host or device.  With K, w and h a point is in the frustum iff all four
+    build_view_frustum(K, 0, 0, w, h) planes . p > 0 (float32 planes, float64 products, as depth_map); without them every point counts.  Only
+    frustum points are queries and only frustum points can be neighbours.  The neighbours of point i are the frustum points j (i included)
+    with d2 = (dx*dx + dy*dy) + dz*dz < radius*radius -- strictly, in float64; the radius is rounded to float32 first (1.0 and 0.5 are exact)
+    -- ordered by (d2, j), the first max_nn (at most 64) kept, a tie at the cut going to the lower index; no cap on the candidates.  With fewer
+    than 3 neighbours the normal is (0, 0, 1); otherwise the unit eigenvector of the smallest eigenvalue of the centred covariance
+    (1 / k) sum (q - m)(q - m)^T, float64, summed in neighbour order; a zero covariance gives (0, 0, 1).  Open3D leaves the sign to its
+    solver; here n . p <= 0 (towards the camera), a product of exactly 0 keeping the solver's sign.  Outside the frustum: (0, 0, 1).
+    The same bits on every run; no host synchronisation.
+    Returns normals float64 [N][3] on the device; with return_info also {'nn_count' int32 [N], 'nn_idx' int32 [N][max_nn] in that order,
+    padded with -1, 'in_frustum' bool [N]}."""
+    dev = _device(lidar)
+    if dev.type != "cuda":
+        raise _lib.SdfrError("lidar_normals runs on the GPU only; there is no CPU fallback")
+    if (K is None) != (w is None) or (K is None) != (h is None):
+        raise ValueError("lidar_normals: K, w and h go together")
+    planes = None if K is None else _frustum(K, w, h)[1]
+    normals, cnt, idx, inside = _normals(_cloud(lidar, dev), planes, radius, max_nn, return_info)
+    return (normals, {"nn_count": cnt, "nn_idx": idx, "in_frustum": inside.bool()}) if return_info else normals
+
+
+@_lib.traced("remove_road")
+def remove_road(lidar, K, w, h, radius=1.0, max_nn=30, cos_thresh=0.9, return_info=False):
+    """The points get_kitti_frame rasterises (utils/refinement.py:623-644): inside the image frustum and not on the road, the road being the
+    points whose normal (lidar_normals, with its untested relation to Open3D) has |n_y| > cos_thresh.  No host synchronisation.
+    Returns keep bool [N] on the device; with return_info also {'normals', 'nn_count', 'in_frustum'}.
+    The reference's plane_normal / plane_offset (:636-640) are computed there but never used, so they are not provided."""
+    dev = _device(lidar)
+    if dev.type != "cuda":
+        raise _lib.SdfrError("remove_road runs on the GPU only; there is no CPU fallback")
+    keep, info = _road_keep(_cloud(lidar, dev), _frustum(K, w, h)[1], radius, max_nn, cos_thresh)
+    return (keep, info) if return_info else keep
+
+
+@_lib.traced("road_free_depth_map")
+def road_free_depth_map(lidar, K, w, h, radius=1.0, max_nn=30, cos_thresh=0.9, return_info=False):
+    """kitti_frame's depth map alone: remove_road, then compute_depth_map over the kept points in input order -- sdfr_depth_map_masked, the
+    last kept point on a pixel wins, so the image has the bits of depth_map(lidar[keep]).  No host synchronisation.
+    Returns depth float32 [h][w] on the device; with return_info also {'keep', 'normals', 'nn_count', 'in_frustum', 'winner' (indices into
+    the WHOLE cloud), 'counts'}."""
+    w, h = int(w), int(h)
+    dev = _device(lidar)
+    if dev.type != "cuda":
+        raise _lib.SdfrError("road_free_depth_map runs on the GPU only; there is no CPU fallback")
+    Kh, planes = _frustum(K, w, h)
+    cam = np.array([Kh[0, 0], Kh[1, 1], Kh[0, 2], Kh[1, 2]], np.float64)
+    pts = _cloud(lidar, dev)
+    keep, info = _road_keep(pts, planes, radius, max_nn, cos_thresh)
+    depth = torch.empty((h, w), dtype=torch.float32, device=dev)
+    winner = torch.empty((h, w), dtype=torch.int32, device=dev)
+    counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    with _lib.guard(dev):
+        ck(_lib.lib().sdfr_depth_map_masked(P(pts), int(pts.dtype == torch.float64), int(pts.shape[0]), P(keep.view(torch.uint8)), planes.ctypes.data,
+                                            cam.ctypes.data, w, h, P(depth), P(winner), P(counts), _lib.stream_ptr()), "sdfr_depth_map_masked")
+    return (depth, dict(info, keep=keep, winner=winner, counts=counts)) if return_info else depth
+
+
+@_lib.traced("kitti_frame")
+def kitti_frame(image, lidar, K, return_info=False, radius=1.0, max_nn=30, cos_thresh=0.9):
+    """get_kitti_frame (utils/refinement.py:612-656) from a raw scan: the frustum cut, remove_road, compute_depth_map over the kept points in
+    input order (road_free_depth_map) and the reprojection of the coloured scene points (reproject_device, as :653).  image: the frame
+    (H, W, 3); lidar [N][3], camera frame.  No host synchronisation.
+    Returns (scene_depth float32 [H][W], pts_scene float32 [H * W][3], clrs_scene float32 [H * W][3]) on the device; the first `count` rows
+    of the last two are the scene's points in row-major pixel order, the rest is unspecified; with return_info a fourth value, a dict with
+    count (int32, on the device) and road_free_depth_map's info.  Not provided: the reference's plane_normal / plane_offset, which it
+    computes but never uses; parsing KITTI3D files stays with the caller."""
+    dev = _device(image, lidar)
+    if dev.type != "cuda":
+        raise _lib.SdfrError("kitti_frame runs on the GPU only; there is no CPU fallback")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    depth, info = road_free_depth_map(lidar, K, w, h, radius, max_nn, cos_thresh, return_info=True)
+    out = reproject_device([image], [depth], [K], device=dev)
+    res = (depth, out["points"][0], out["colors"][0])
+    return res + (dict(info, count=out["cnt"][0]),) if return_info else res

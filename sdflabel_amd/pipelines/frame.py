@@ -4,9 +4,10 @@ annotations.  It contains nothing but calls of the public stages, in the referen
     from sdflabel_amd.pipelines.frame import refine_frame
 
 refine_frame starts from finished crops.  refine_sample starts from a loaded KITTI sample: it selects the annotations, builds the depth map
-from the lidar if asked, matches the detector's boxes, cuts the crops on the device, prepares the CSS network's input, runs the network once
-over all crops and hands the result to refine_frame.  What stays with the caller: loading the frame (datasets/kitti.py, the road-plane
-removal of get_kitti_frame) and the CSS network itself, which is any torch.nn.Module passed in.
+from the lidar if asked -- with remove_road=True from the raw scan, the road plane removed first as get_kitti_frame does --, matches the
+detector's boxes, cuts the crops on the device, prepares the CSS network's input, runs the network once over all crops and hands the result
+to refine_frame.  What stays with the caller: loading the frame (datasets/kitti.py) and the CSS network itself, which is any
+torch.nn.Module passed in.
 """
 from collections import defaultdict
 
@@ -16,7 +17,7 @@ import torch.nn.functional as F
 
 from .. import _lib
 from ..frame import (NECESSARY_KEYS, _as_tensor, css_inputs_many, depth_map, frame_dict, init_params_many, labels_many, match_boxes,
-                     reproject_many, surfaces_many)
+                     reproject_many, road_free_depth_map, surfaces_many)
 from .optimizer import optimize_many
 from .pose import PoseEstimator
 from .refinement import adjust_intrinsics_crop, get_annos
@@ -69,12 +70,15 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
 
 def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_annos='', label_type='gt', maskrcnn_labels=None, lidar=None,
                   css_batch=None, pose_type='kabsch', scale=2.0, rendering_area=32, sampler='device', seed=0, keys=None, optimize_kwargs=None,
-                  return_stages=False):
+                  return_stages=False, remove_road=False):
     """One KITTI sample from the loaded frame to the evaluator's dicts: the body of the reference's frame loop (refine_css.py:94-245).
 
     sample: {'image' (H, W, 3) float32 BGR in 0 ... 1, 'orig_cam' 3x3, 'world_to_cam' 4x4, 'annos' {'easy', 'medium', 'hard'} and 'depth'
     (H, W), the sparse depth map}.  With `lidar` ([N][3], camera frame, already restricted to what should be rasterised -- the reference
-    removes the road plane first) the depth map is built by frame.depth_map instead and sample['depth'] is not read.
+    removes the road plane first) the depth map is built by frame.depth_map instead and sample['depth'] is not read.  With `lidar` and
+    remove_road=True the lidar is the raw scan and the depth map is frame.kitti_frame's (road_free_depth_map): the road plane is removed on the device first, as
+    get_kitti_frame does (the normals are frame.lidar_normals' own statement of Open3D's; parity with Open3D is untested).  That adds no
+    host synchronisation.
     css_net: a module mapping [n][3][128][128] to {'uvw_sm_masked', 'latent'}; the shipped one is sdflabel_amd.networks.resnet_css.setup_css
     (the reference's network with its output head fused on the device, loads a reference css.pt).  annos: the annotations to label; None selects them with
     get_annos(diff_annos, sample).  label_type: 'gt' (the annotations' own boxes), 'rcnn' or 'maskrcnn' with maskrcnn_labels = {'bboxes'
@@ -118,7 +122,12 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
     image = _as_tensor(sample['image'], device)
     H, W = int(image.shape[0]), int(image.shape[1])
     K_orig = sample['orig_cam']
-    depth = depth_map(lidar, K_orig, W, H) if lidar is not None else _as_tensor(sample['depth'], device)
+    if remove_road and lidar is None:
+        raise ValueError("refine_sample: remove_road=True needs the lidar scan")
+    if lidar is None:
+        depth = _as_tensor(sample['depth'], device)
+    else:
+        depth = road_free_depth_map(lidar, K_orig, W, H) if remove_road else depth_map(lidar, K_orig, W, H)
     # boxes
     live = list(range(len(annos)))
     boxes = [[int(v) for v in np.asarray(a['bbox']).tolist()] if label_type == 'gt' else None for a in annos]

@@ -5,8 +5,8 @@ import line:
 
 Ported: reproject, get_kitti_label, roty_in_bev, alpha_in_bev, compute_iou, get_iou, adjust_intrinsics_crop, rot_from_yaw, compute_depth_map,
 build_view_frustum, build_cam_frustum, unproject, transform_bgr_crop, get_annos, is_anno_easy / _moderate / _hard -- same signatures, same
-return values.  The remaining dataset, visualisation and cv2 helpers of that module (get_kitti_frame with its open3d road-plane removal,
-project, the open3d line sets, ...) are not ported, which is why there is no module of that name under compat/: it would shadow them.
+return values -- and get_kitti_frame, whose differences are listed below.  The remaining dataset, visualisation and cv2 helpers of that
+module (project, the open3d line sets, ...) are not ported, which is why there is no module of that name under compat/: it would shadow them.
 
 Differences from the reference, all deliberate:
   - reproject of numpy inputs runs on the device in float32 like the torch branch and returns float32 numpy arrays (the reference's numpy
@@ -15,6 +15,9 @@ Differences from the reference, all deliberate:
   - compute_depth_map drops a point that float32 rounding puts at x == w or y == h, where the reference raises IndexError;
   - transform_bgr_crop needs neither cv2, PIL nor torchvision: PIL's 8-bit bilinear resize is reproduced byte for byte on the device; it
     returns CPU tensors, as the reference does, and does not modify crop_bgr;
+  - get_kitti_frame needs no open3d: the normals of its road-plane removal follow frame.lidar_normals' own statement of Open3D's hybrid
+    search and covariance normals (Open3D is not installed where this was developed: parity with it is untested); it returns the depth map
+    as a device tensor and a ScenePoints object in the o3d.geometry.PointCloud's place;
   - cv2.undistortPoints / cv2.projectPoints are taken to be the plain pinhole (cv2 is not installed where this was developed: untested).
 A frame's annotations are better served by sdflabel_amd.frame (reproject_many, init_params_many, labels_many, css_inputs_many): one launch
 sequence and one synchronisation per stage instead of one per annotation; pipelines.frame.refine_sample is the whole loop for a sample.
@@ -23,7 +26,7 @@ import numpy as np
 import torch
 
 from ..frame import (adjust_intrinsics_crop, alpha_in_bev, build_cam_frustum, build_view_frustum, compute_iou, css_inputs_many,  # noqa: F401
-                     depth_map, get_iou, labels_many, reproject_many, rot_from_yaw, roty_in_bev, unproject)
+                     depth_map, get_iou, kitti_frame, labels_many, reproject_many, rot_from_yaw, roty_in_bev, unproject)
 
 
 def is_anno_easy(anno):
@@ -91,3 +94,48 @@ def get_kitti_label(dsdf, grid, latent, scale, trans, yaw, p_WC, bbox):
         raise ValueError("get_kitti_label: no grid point within the band of the zero level set (zero-size array to reduction operation)")
     label, scaled_points, cam_T = res
     return label, np.asarray(scaled_points), cam_T
+
+
+class ScenePoints:
+    """What get_kitti_frame returns in the o3d.geometry.PointCloud's place: `.points` and `.colors`, each converting with np.asarray to the
+    float64 [n][3] array open3d's Vector3dVector would hold (float32 values, widened).  The data stays on the device until one of them is
+    converted -- the read of the point count is the one host synchronisation, made then and not before; `.device()` gives the (points,
+    colors) float32 device tensors.  No open3d methods (normals, visualisation) are offered."""
+
+    class _Lazy:
+        def __init__(self, owner, k):
+            self._owner, self._k = owner, k
+
+        def __array__(self, dtype=None, copy=None):
+            a = self._owner._fetch()[self._k]
+            return a if dtype is None else a.astype(dtype)
+
+        def __len__(self):
+            return len(self._owner._fetch()[self._k])
+
+    def __init__(self, points, colors, count):
+        self._p, self._c, self._n, self._host = points, colors, count, None
+        self.points, self.colors = ScenePoints._Lazy(self, 0), ScenePoints._Lazy(self, 1)
+
+    def device(self):
+        n = int(self._n)
+        return self._p[:n], self._c[:n]
+
+    def _fetch(self):
+        if self._host is None:
+            p, c = self.device()
+            self._host = (p.cpu().numpy().astype(np.float64), c.cpu().numpy().astype(np.float64))
+        return self._host
+
+
+def get_kitti_frame(sample):
+    """utils/refinement.py:612-656: (scene_depth, pcd) of a loaded KITTI sample {'image' (H, W, 3), 'lidar' [N][3] in the camera frame,
+    'orig_cam' 3x3}: the lidar cut to the image frustum, the road plane removed by the normal test |n_y| > 0.9, the rest rasterised into the
+    sparse depth map, and the coloured scene points reprojected from it -- frame.kitti_frame, no host synchronisation.
+    Differences from the reference: scene_depth is a float32 device tensor (H, W) where the reference returns a numpy array (.cpu().numpy()
+    gives it); pcd is a ScenePoints, not an o3d.geometry.PointCloud: `.points` and `.colors` convert with np.asarray, nothing else of open3d's
+    class is offered.  The normals are frame.lidar_normals' -- written from Open3D's algorithm, parity with Open3D untested.  The reference's
+    plane_normal / plane_offset are computed there but never used, so they are not provided.  Parsing the KITTI3D files into the sample
+    (datasets/kitti.py) stays with the caller."""
+    depth, pts, clrs, info = kitti_frame(sample['image'], sample['lidar'], sample['orig_cam'], return_info=True)
+    return depth, ScenePoints(pts, clrs, info["count"])
