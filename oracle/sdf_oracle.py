@@ -437,8 +437,8 @@ def inside_circle_opt(K, vertex_2d, vertex_3d, diam=0.025, depth_constant=10000,
     ids[..., 0] = np.clip(ids[..., 0], 0, x_px - 1)
     ids[..., 1] = np.clip(ids[..., 1], 0, y_px - 1)
     N = vertex_3d.shape[0]
-    dense = np.zeros((N, y_px, x_px), np.float32)
-    np.add.at(dense, (np.arange(N)[:, None], ids[..., 1], ids[..., 0]), prim.astype(np.float32))
+    dense = np.zeros((N, y_px, x_px), dt)                                                            # (the reference's sparse tensor is float32, :135-138: the dtype follows the input here)
+    np.add.at(dense, (np.arange(N)[:, None], ids[..., 1], ids[..., 0]), prim.astype(dt))
     m = dense.reshape(N, -1) > 0                                                                     # :155
     zl, _, _ = depth_logits(vertex_3d, depth_constant)
     L = np.broadcast_to(zl[:, None], m.shape).astype(dt)

@@ -89,25 +89,109 @@ def project_in_2D(K, pose, points, normals, res):
     return out
 
 
-def inside_surfel(K, grid_2d, vertex_3d, normals, diam=0.04, depth_constant=150):
-    """primitives.py:165-242 with softclamp=False, add_bg=False: the dense (N, P) weights."""
+def _bg_row(z, mask, z_bg):
+    """the background row of the primitives (:64-67, :146-153, :233-237): its logit and a mask row of ones"""
+    return torch.cat([z, z_bg.reshape(1, 1).expand(1, z.shape[1]).to(z.dtype)]), torch.cat([mask, torch.ones_like(mask[:1])])
+
+
+def inside_surfel(K, grid_2d, vertex_3d, normals, diam=0.04, depth_constant=150, softclamp=False, softclamp_constant=5, add_bg=False,
+                  bg_logit=None, Kinv=None, eps=None):
+    """primitives.py:165-242: the dense (N[+1], P) weights.  Defaults: softclamp=False, add_bg=False (the renderer's call).  bg_logit: the
+    background row's logit handed in as a constant (what the HIP kernels receive) instead of computed from the depths (:234-235);
+    Kinv / eps: the inverse intrinsics and the epsilon to use instead of K.float().inverse() / finfo(dtype).eps (float64 restatements of
+    the float32 computation)."""
     dt = K.dtype
-    eps = torch.finfo(dt).eps
+    eps = torch.finfo(dt).eps if eps is None else eps
     n_v3d = (normals * vertex_3d).sum(1)                                                 # :202
     g = torch.cat([grid_2d[0].to(dt), torch.ones_like(grid_2d[0][:, :1]).to(dt)], -1)    # :203-207
-    rays = (K.float().inverse() @ g.t()).t()                                             # :204-208
+    Ki = K.float().inverse().to(dt) if Kinv is None else Kinv
+    rays = (Ki @ g.t()).t()                                                              # :204-208
     b = (normals @ rays.t())                                                             # :209  (N, P)
     b[b.abs() < 0.01] = eps                                                              # :210 (in place: no gradient through the overwritten entries)
     z = n_v3d.unsqueeze(-1) / b                                                          # :211
     g3 = rays.unsqueeze(0) * z.unsqueeze(-1)                                             # :212  (N, P, 3)
     d = (vertex_3d.view(-1, 1, 3) - g3).pow(2).sum(-1).sqrt()                            # :215,:220
-    dist = torch.clamp(diam - d, min=0)                                                  # :220
+    if softclamp:
+        dist = torch.sigmoid((diam - d) * softclamp_constant)                            # :217-218
+    else:
+        dist = torch.clamp(diam - d, min=0)                                              # :220
     mask = (dist > 0).detach().to(dt)                                                    # :226
     zz = -z * mask                                                                       # :227
     zn = torch.norm(zz, p=2, dim=0).detach().unsqueeze(0)                                # :228
     zz = torch.clamp(zz / (zn + eps) + 1, min=0) * depth_constant                        # :229-230
+    if bg_logit is not None or add_bg:
+        z_bg = torch.as_tensor(bg_logit, dtype=dt) if bg_logit is not None else (-vertex_3d[:, 2] * depth_constant).min() - 1   # :234-235
+        zz, mask = _bg_row(zz, mask, z_bg)                                               # :236-237
     zz = zz.masked_fill(mask == 0, torch.finfo(dt).min)                                  # :240
     return F.softmax(zz, dim=0) * mask                                                   # :240
+
+
+def _depth_logits(vertex_3d, depth_constant, eps, znorm=None):
+    """:56-61 / :141-144: clamp(-z / (||z|| + eps) + 1, 0) * C, the norm detached (znorm: handed in as a constant)"""
+    z = -vertex_3d[:, 2:]
+    zn = torch.norm(z, p=2, dim=0).detach() if znorm is None else znorm
+    return torch.clamp(z / (zn + eps) + 1, min=0) * depth_constant
+
+
+def inside_circle(K, grid_2d, vertex_2d, vertex_3d, diam=0.02, depth_constant=100, softclamp=True, softclamp_constant=3, add_bg=False,
+                  bg_logit=None, znorm=None, eps=None):
+    """primitives.py:4-71: 2-D circles; the softmax runs over z * mask (:70), so uncovered vertices keep a logit of 0."""
+    dt = K.dtype
+    eps = torch.finfo(dt).eps if eps is None else eps
+    diff = vertex_2d[:, :2].view(-1, 1, 2) - grid_2d.to(dt)                               # :42
+    rad = (K[0, 0] * diam / (vertex_3d[:, 2] + eps)).abs().unsqueeze(-1)                  # :47
+    if softclamp:
+        dist = torch.sigmoid((rad - diff.pow(2).sum(-1).sqrt()) * softclamp_constant)    # :46-49
+    else:
+        dist = torch.clamp(rad - diff.pow(2).sum(-1).sqrt(), min=0)                      # :51-53
+    mask = (dist > 0).detach().to(dt)                                                    # :55
+    z = _depth_logits(vertex_3d, depth_constant, eps, znorm)                              # :56-61
+    if bg_logit is not None or add_bg:
+        z_bg = torch.as_tensor(bg_logit, dtype=dt) if bg_logit is not None else z.min() - 1   # :65
+        z = torch.cat([z, z_bg.reshape(1, 1)])                                           # :66
+        mask = torch.cat([mask, torch.ones_like(mask[:1])])                              # :67
+    return torch.softmax(z * mask, dim=0) * mask                                         # :70
+
+
+def inside_circle_opt(K, vertex_2d, vertex_3d, res, diam=0.025, depth_constant=10000, softclamp=True, softclamp_constant=5, add_bg=False,
+                      bg_logit=None, znorm=None, eps=None):
+    """primitives.py:74-162: every vertex stamps the 15 x 15 offsets around trunc(vertex_2d + offset), indices clamped into the image
+    (res = (W, H); the reference takes it from K, :109-110), duplicates summed (:135-138); coverage = stamped value > 0 (:155)."""
+    dt = K.dtype
+    eps = torch.finfo(dt).eps if eps is None else eps
+    W, H = res
+    yy, xx = np.mgrid[-7:8, -7:8]
+    off = torch.from_numpy(np.stack((xx, yy), axis=-1).reshape(-1, 2)).to(dt)             # rasterer.py:30-32
+    rad = (K[0, 0] * diam / (vertex_3d[:, 2] + eps)).abs()                                # :115
+    dprim = off.pow(2).sum(-1).sqrt()                                                     # :114
+    if softclamp:
+        prim = torch.sigmoid((rad.unsqueeze(-1) - dprim) * softclamp_constant)           # :118
+    else:
+        prim = torch.clamp(rad.unsqueeze(-1) - dprim, min=0)                             # :120
+    ids = (off.unsqueeze(0) + vertex_2d.detach().unsqueeze(-2)).long()                    # :122-124
+    ix = ids[..., 0].clamp(0, W - 1)                                                      # :125-127
+    iy = ids[..., 1].clamp(0, H - 1)
+    N = vertex_3d.shape[0]
+    dense = torch.zeros((N, H * W), dtype=dt)
+    dense.scatter_add_(1, iy * W + ix, prim.detach())                                    # :130-138
+    mask = (dense > 0).to(dt)                                                            # :155
+    z = _depth_logits(vertex_3d, depth_constant, eps, znorm).expand(-1, H * W)            # :141-144
+    if bg_logit is not None or add_bg:
+        z_bg = torch.as_tensor(bg_logit, dtype=dt) if bg_logit is not None else z.min() - 1   # :147
+        z, mask = _bg_row(z, mask, z_bg)                                                 # :148-153
+    return torch.softmax(z.masked_fill(mask == 0, torch.finfo(dt).min), dim=0) * mask    # :156
+
+
+def composite(prob, col_attr, v3, nrm, bg=None):
+    """rasterer.py:107-144 for a dense weight matrix (N[+1], P): colour (with the background image on the last row, :107-111), mask,
+    depth and normal images, clamped at 1 where the reference clamps; (3 | 1, P) each."""
+    N = v3.shape[0]
+    w = prob[:N]
+    color = w.t().matmul(col_attr).t()
+    if bg is not None:
+        color = color + prob[N:N + 1] * bg.reshape(3, -1)
+    return {"color": torch.clamp(color, max=1), "mask": torch.clamp(prob.sum(0, keepdim=True), max=1),
+            "depth": (w * v3[:, 2:3]).sum(0, keepdim=True), "normals": torch.clamp(w.t().matmul((nrm + 1) / 2).t(), max=1)}
 
 
 def rasterer_forward(K, res, coords, normals, pose, output_depth=False):
