@@ -4,11 +4,9 @@
 //                  them per pixel: log_softmax, softmax(100 .), the expected colour sum_k k p_k, the soft mask, the arg-max mask and the masked
 //                  product.  A 64 -> 768 GEMM with a per-pixel reduction epilogue: nothing 256 channels wide is written unless the caller asks
 //                  for the log-probabilities.
-//                    - Logits: exact-f32 MFMA (v_mfma_f32_32x32x2_f32), A = the head's weights from LDS, B = the features straight from global
-//                      memory (NCHW: a k-row of 32 pixels is one 128-byte line).  k runs 0 ... 63 in order from a zero accumulator for every class
-//                      and every pixel, the bias is added last: an fmaf chain, bit for bit.
-//                    - A wave owns 32 pixels and all 256 classes (8 accumulator tiles); pixel p's logits sit in lanes p and p + 32, 128 registers
-//                      each, so every reduction is over a lane's registers in a fixed order plus one exchange with lane ^ 32.
+//                    - Logits: css_logits_tile of css_tile.h (exact-f32 MFMA, k in order, bias last; a wave owns 32 pixels and all 256
+//                      classes, pixel p's logits sit in lanes p and p + 32), the function the training kernels of css_train.hip call too.
+//                      Every reduction is over a lane's registers in a fixed order plus one exchange with lane ^ 32.
 //                    - softmax(100 log_softmax(u)) == softmax(100 u): the colour path never forms the log-softmax.  The maximum is subtracted
 //                      first, exp runs in float32 (expf), the two sums accumulate in float64 (k e is exact there) in class order.
 //                      A class whose 100 (logit - max) is below -104 in all 64 lanes is skipped: expf returns exactly 0 there.
@@ -16,14 +14,8 @@
 //                    - No atomics; a pixel's result depends on its own 4 x 64 features and the weights only: not on B, the tile or the launch.
 // sdfr_css_latent  out_lat (1x1 conv 256 -> 3) on x4, the mean over the pixels and the projection onto the unit sphere; one workgroup per crop.
 // Compiled with -ffp-contract=off: the fused operations are the explicit fmaf / MFMA chains only.
-#include "sdfr_common.h"
+#include "css_tile.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define CH_K 64                    // input channels of the head
-#define CH_N 256                   // classes per colour head
-#define CH_LD 257                  // LDS image W^T [k][class], row pitch in dwords (257: the transposing store is conflict free)
-#define CH_TILE 128                // pixels per workgroup pass: 4 waves x 32
 #define CH_SKIP (-104.0f)          // expf(x) == 0 for x < -103.98 (below half the smallest subnormal)
 #define CH_HARD 100.0f             // sm_hardness of the reference
 
@@ -43,91 +35,46 @@ struct CssHeadArgs {
     int64_t n_tiles;               // B * tiles_per_crop
 };
 
-// class of accumulator register r of tile t in lane half h (C/D map of the 32x32 MFMA: row = (r & 3) + 8 (r >> 2) + 4 h)
-#define CH_CLASS(t, r, h) (32 * (t) + ((r) & 3) + 8 * ((r) >> 2) + 4 * (h))
-
 __global__ __launch_bounds__(256, 2) void sdfr_css_head_kernel(CssHeadArgs A) {
     extern __shared__ float smem[];
-    float* wT = smem;                              // [64][CH_LD]
-    float* bs = smem + CH_K * CH_LD;               // [256] bias, then [128] mask weights, [2] mask bias
-    float* wms = bs + CH_N;
+    float* wT = smem;                              // [64][CSS_LD]
+    float* bs = smem + CSS_K * CSS_LD;             // [256] bias, then [128] mask weights, [2] mask bias
+    float* wms = bs + CSS_N;
     const int head = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 31, h = lane >> 5;
 
-    // the head's weights, transposed: thread reads W[c][4 q ... 4 q + 3] (coalesced), writes wT[4 q + i][c]
-    {
-        const float4* W4 = reinterpret_cast<const float4*>(A.w[head]);
-        for (int i = tid; i < CH_N * CH_K / 4; i += 256) {
-            const float4 v = W4[i];
-            const int c = i >> 4, k = (i & 15) * 4;
-            wT[(k + 0) * CH_LD + c] = v.x;
-            wT[(k + 1) * CH_LD + c] = v.y;
-            wT[(k + 2) * CH_LD + c] = v.z;
-            wT[(k + 3) * CH_LD + c] = v.w;
-        }
-        bs[tid] = A.b[head][tid];
-        if (tid < 2 * CH_K) wms[tid] = A.wm[tid];
-        if (tid < 2) wms[2 * CH_K + tid] = A.bm[tid];
-    }
+    css_stage_weights<CSS_N>(A.w[head], A.b[head], wT, bs, tid);
+    if (tid < 2 * CSS_K) wms[tid] = A.wm[tid];
+    if (tid < 2) wms[2 * CSS_K + tid] = A.bm[tid];
     __syncthreads();
 
     const int HW = A.HW;
     for (int64_t tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
-        const int b = (int)(tile / A.tiles_per_crop);
-        const int pix = (int)(tile % A.tiles_per_crop) * CH_TILE + wave * 32 + col;
-        const bool live = pix < HW;
-        if (wave * 32 + (int)(tile % A.tiles_per_crop) * CH_TILE >= HW) continue;          // the whole wave is past the crop (wave-uniform)
-        const int p = live ? pix : 0;                                                          // a dead lane reads pixel 0 and stores nothing
+        const CssLane L = css_tile_lane(tile, A.tiles_per_crop, HW, wave, col);
+        if (L.wave_past_crop) continue;
+        const int b = L.b, pix = L.pix, p = L.p;
+        const bool live = L.live;
 
-        // ---- B operands: x[b][2 s + h][pix], one register per MFMA step, fetched 8 steps ahead of their use
-        const float* xh = A.x[head] + ((int64_t)b * CH_K + h) * HW + p;
+        // ---- B operands: x[b][2 s + h][pix], one register per MFMA step, fetched 8 steps ahead of their use: before the mask chain
+        const float* xh = A.x[head] + ((int64_t)b * CSS_K + h) * HW + p;
         float xb[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) xb[s] = live ? xh[(int64_t)(2 * s) * HW] : 0.f;
+        css_prefetch8(xh, HW, live, xb);
 
         // ---- the mask logit of row h for this pixel (both halves of the wave work: row 0 in lanes 0-31, row 1 in lanes 32-63)
         float mh = 0.f;
         {
-            const float* xm = A.xm + (int64_t)b * CH_K * HW + p;
-            const float* wr = wms + h * CH_K;
+            const float* xm = A.xm + (int64_t)b * CSS_K * HW + p;
+            const float* wr = wms + h * CSS_K;
 #pragma unroll 16
-            for (int k = 0; k < CH_K; ++k) mh = fmaf(wr[k], xm[(int64_t)k * HW], mh);
-            mh = mh + wms[2 * CH_K + h];
+            for (int k = 0; k < CSS_K; ++k) mh = fmaf(wr[k], xm[(int64_t)k * HW], mh);
+            mh = mh + wms[2 * CSS_K + h];
         }
         const float mo = __shfl_xor(mh, 32);
         const float m0 = h ? mo : mh, m1 = h ? mh : mo;
 
-        // ---- logits: 8 tiles of 32 classes x 32 pixels, k in order
+        // ---- logits: 8 tiles of 32 classes x 32 pixels, k in order, bias last, and the per-pixel maximum
         f32x16 acc[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-        const float* wa = wT + h * CH_LD + col;
-#pragma unroll 1
-        for (int g = 0; g < 4; ++g) {
-            float xn[8];
-#pragma unroll
-            for (int s = 0; s < 8; ++s) xn[s] = (live && g < 3) ? xh[(int64_t)(2 * (8 * (g + 1) + s)) * HW] : 0.f;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-#pragma unroll
-                for (int t = 0; t < 8; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[2 * (8 * g + s) * CH_LD + 32 * t], xb[s], acc[t], 0, 0, 0);
-            }
-#pragma unroll
-            for (int s = 0; s < 8; ++s) xb[s] = xn[s];
-        }
-        // bias last, then the per-pixel maximum
-        float mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                acc[t][r] = acc[t][r] + bs[CH_CLASS(t, r, h)];
-                mx = fmaxf(mx, acc[t][r]);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float mx = css_logits_tile(wT, bs, xh, HW, live, col, h, xb, acc);
 
         // ---- expected colour: sum k e / sum e, e = exp(100 (logit - max)); float64 sums, classes in register order, half 0 before half 1
         double se = 0.0, sk = 0.0;
@@ -139,12 +86,11 @@ __global__ __launch_bounds__(256, 2) void sdfr_css_head_kernel(CssHeadArgs A) {
                 if (__builtin_amdgcn_ballot_w64(a >= CH_SKIP) != 0ull) {
                     const double e = (double)expf(a);
                     se += e;
-                    sk = fma((double)CH_CLASS(t, r, 0), e, sk);          // the half's 4 h is added once below
+                    sk = fma((double)CSS_CLASS(t, r, 0), e, sk);          // the half's 4 h is added once below
                 }
             }
         sk = fma((double)(4 * h), se, sk);
-        const double se_o = __shfl_xor(se, 32), sk_o = __shfl_xor(sk, 32);
-        const double S = h ? se_o + se : se + se_o, N = h ? sk_o + sk : sk + sk_o;
+        const double S = css_pair_sum(se, h), N = css_pair_sum(sk, h);
         const float colour = (float)(N / S);
 
         // ---- mask: raw logits, softmax(100 .)[1], arg-max (a tie is class 0)
@@ -172,14 +118,13 @@ __global__ __launch_bounds__(256, 2) void sdfr_css_head_kernel(CssHeadArgs A) {
             for (int t = 0; t < 8; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s1 += (double)expf(acc[t][r] - mx);
-            const double s1_o = __shfl_xor(s1, 32);
-            const float lse = (float)log(h ? s1_o + s1 : s1 + s1_o);
+            const float lse = (float)log(css_pair_sum(s1, h));
             if (live) {
-                float* d = lp + ((int64_t)b * CH_N + 4 * h) * HW + pix;
+                float* d = lp + ((int64_t)b * CSS_N + 4 * h) * HW + pix;
 #pragma unroll
                 for (int t = 0; t < 8; ++t)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) d[(int64_t)CH_CLASS(t, r, 0) * HW] = (acc[t][r] - mx) - lse;
+                    for (int r = 0; r < 16; ++r) d[(int64_t)CSS_CLASS(t, r, 0) * HW] = (acc[t][r] - mx) - lse;
             }
         }
     }
@@ -211,12 +156,7 @@ __global__ __launch_bounds__(256) void sdfr_css_latent_kernel(const float* __res
         s[2] += a2 + bias[2];
     }
     for (int c = 0; c < 3; ++c) red[c][tid] = s[c];
-    __syncthreads();
-    for (int n = 128; n > 0; n >>= 1) {                    // fixed tree: the same order whatever B is
-        if (tid < n)
-            for (int c = 0; c < 3; ++c) red[c][tid] += red[c][tid + n];
-        __syncthreads();
-    }
+    css_tree_sum256<3>(&red[0][0], tid);
     if (tid == 0) {
         const float v0 = red[0][0] / (float)hw, v1 = red[1][0] / (float)hw, v2 = red[2][0] / (float)hw;
         const float len = sqrtf((v0 * v0 + v1 * v1) + v2 * v2);
@@ -227,23 +167,12 @@ __global__ __launch_bounds__(256) void sdfr_css_latent_kernel(const float* __res
     }
 }
 
-// the launch dereferences the caller's pointers from the stream of the CURRENT device: refuse a call whose data lives elsewhere, as the decoder
-// launches do for their weight images
-static int css_device_check(const void* p, const char* what) {
-    int cur = -1;
-    SDFR_HIP_CHECK(hipGetDevice(&cur));
-    hipPointerAttribute_t at;
-    SDFR_HIP_CHECK(hipPointerGetAttributes(&at, p));
-    SDFR_REQUIRE(at.device == cur, "%s: the tensors live on device %d but the current device (the launch stream's) is %d", what, at.device, cur);
-    return SDFR_OK;
-}
-
 extern "C" int sdfr_css_head(const float* x_u, const float* x_v, const float* x_w, const float* x_mask, int B, int C, int H, int W,
                              const float* w_u, const float* b_u, const float* w_v, const float* b_v, const float* w_w, const float* b_w,
                              const float* w_mask, const float* b_mask, float* uvw_sm, float* uvw_sm_masked, float* mask, float* mask_sm,
                              float* u, float* v, float* w, void* stream) {
     SDFR_REQUIRE(B >= 0 && H >= 0 && W >= 0, "sdfr_css_head: negative size");
-    SDFR_REQUIRE(C == CH_K, "sdfr_css_head: the head takes %d feature channels (got %d)", CH_K, C);
+    SDFR_REQUIRE(C == CSS_K, "sdfr_css_head: the head takes %d feature channels (got %d)", CSS_K, C);
     SDFR_REQUIRE((int64_t)H * W < (1ll << 30), "sdfr_css_head: H * W = %lld is beyond 2^30", (long long)H * W);
     if (B == 0 || H == 0 || W == 0) return SDFR_OK;
     SDFR_REQUIRE(x_u && x_v && x_w && x_mask && w_u && b_u && w_v && b_v && w_w && b_w && w_mask && b_mask, "sdfr_css_head: NULL input");
@@ -257,7 +186,7 @@ extern "C" int sdfr_css_head(const float* x_u, const float* x_v, const float* x_
     A.uvw_sm = uvw_sm; A.uvw_sm_masked = uvw_sm_masked; A.mask = mask; A.mask_sm = mask_sm;
     A.lp[0] = u; A.lp[1] = v; A.lp[2] = w;
     A.HW = H * W;
-    A.tiles_per_crop = sdfr_cdiv(A.HW, CH_TILE);
+    A.tiles_per_crop = sdfr_cdiv(A.HW, CSS_TILE);
     A.n_tiles = (int64_t)B * A.tiles_per_crop;
     // two workgroups fit a CU (64 KB of LDS each); three heads share the device, so each gets a third of the slots and walks its tiles
     int dev = 0, cus = 0;
@@ -266,7 +195,7 @@ extern "C" int sdfr_css_head(const float* x_u, const float* x_v, const float* x_
     int64_t gx = (int64_t)(cus > 0 ? cus : 256) * 2 / 3;
     if (gx < 1) gx = 1;
     if (gx > A.n_tiles) gx = A.n_tiles;
-    const size_t lds = (size_t)(CH_K * CH_LD + CH_N + 2 * CH_K + 2) * sizeof(float);
+    const size_t lds = (size_t)(CSS_K * CSS_LD + CSS_N + 2 * CSS_K + 2) * sizeof(float);
     // (more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device's image of the kernel, so it is set at every call)
     SDFR_HIP_CHECK(hipFuncSetAttribute((const void*)sdfr_css_head_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(sdfr_css_head_kernel, dim3((unsigned)gx, 3), dim3(256), lds, (hipStream_t)stream, A);

@@ -7,16 +7,17 @@
 //   loss_latent = mean((lat - gt)^2), lat = v / (|v| + 1e-8) with the length DETACHED as in the reference: dlat/dv = 1 / (|v| + 1e-8)
 //
 // sdfr_css_head_loss   four launches on one stream:
-//   css_loss_fwd_kernel   the forward's logits tile (css_head.hip: a wave owns 32 pixels x 256 classes, 8 accumulator tiles of
-//                         v_mfma_f32_32x32x2_f32, k in order, bias last), the per-pixel maximum, log-sum-exp and target logit (compare against
-//                         the class number of each register), g = m (exp(z - lse) - onehot) / N over the accumulators, then
+//   css_loss_fwd_kernel   css_logits_tile of css_tile.h, the function sdfr_css_head_kernel calls (a wave owns 32 pixels x 256 classes, 8
+//                         accumulator tiles of v_mfma_f32_32x32x2_f32, k in order, bias last, the per-pixel maximum): the inference path's
+//                         logits by construction.  Then log-sum-exp and target logit (compare against the class number of each register),
+//                         g = m (exp(z - lse) - onehot) / N over the accumulators, then
 //                         dX[k][pix] = sum_c W[c][k] g[c][pix]: accumulator register r of tile t IS the B operand (its two k-slots are the
 //                         classes of lane halves 0 and 1), the A operand W[class][32 mt + col] comes from the same LDS image W^T [k][class] the
-//                         forward uses: at pitch 257 the 32 lanes of a ds_read_b32 group hit 32 banks.  The per-pixel lse (4 bytes per pixel
-//                         and head) goes to the workspace; loss sums are float64 per workgroup.
+//                         logits read (css_stage_weights): at pitch 257 the 32 lanes of a ds_read_b32 group hit 32 banks.  The per-pixel lse
+//                         (4 bytes per pixel and head) goes to the workspace; loss sums are float64 per workgroup.
 //   css_loss_dw_kernel    dW[c][k] = sum_pix g[c][pix] x[k][pix] needs the pixels in the reduction slot: a second pass recomputes the logits
-//                         TRANSPOSED (the forward's MFMA with A and B swapped: the same products in the same order) from the stored lse, so
-//                         that a lane owns a class and its registers are pixels; that register is the A operand of the dW MFMA, the B operand
+//                         TRANSPOSED (css_logits_tile's MFMA with A and B swapped: the same products in the same order) from the stored lse,
+//                         so that a lane owns a class and its registers are pixels; that register is the A operand of the dW MFMA, the B operand
 //                         x[k][pix] comes from an LDS copy of the wave's 64 x 32 feature tile.  A workgroup owns half the classes (128
 //                         accumulator registers per wave), walks its tiles, sums its four waves in order and writes ONE partial dW / db.
 //   css_loss_mask_kernel  the 64 -> 2 mask head on fmaf chains, a thread per pixel; its dW through an LDS copy of the tile.
@@ -24,24 +25,16 @@
 // The partials' size depends on the (fixed) grid only.  No atomics: every output has the same bits in every run.
 // sdfr_css_latent_loss  one workgroup per crop, then a reduction over the crops in order.
 // Compiled with -ffp-contract=off: the fused operations are the explicit fmaf / MFMA chains only.
-#include "sdfr_common.h"
+#include "css_tile.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define CT_K 64                    // input channels of the head
-#define CT_N 256                   // classes per colour head
-#define CT_LD 257                  // LDS image W^T [k][class], row pitch in dwords
-#define CT_LDH 129                 // the same for half the classes (dW pass)
+#define CT_NH (CSS_N / 2)           // classes of a dW workgroup; its LDS image W^T [k][class] has pitch CT_NH + 1
+#define CT_LDH (CT_NH + 1)
 #define CT_XP 33                   // pitch of a wave's feature tile [k][32 pixels] in LDS
-#define CT_TILE 128                // pixels per workgroup pass: 4 waves x 32
 #define CT_GX 80                   // workgroups per colour head (fixed: the partials' size and the summation order do not depend on the device)
 #define CT_MTILE 256               // pixels per pass of the mask kernel
+#define CT_MLD (CT_MTILE + 1)      // pitch of its feature tile [k][256 pixels] in LDS
 #define CT_MGX 128                 // workgroups of the mask kernel
 #define CT_LN256 5.5451774444795624753
-
-// row of accumulator register r in lane half h (C/D map of the 32x32 MFMA)
-#define CT_ROW(r, h) (((r) & 3) + 8 * ((r) >> 2) + 4 * (h))
-#define CT_CLASS(t, r, h) (32 * (t) + CT_ROW(r, h))
 
 // workspace layout (bytes): doubles first
 //   double part_loss[3][CT_GX][2]   (sum over foreground pixels of lse - z[t], number of foreground pixels)
@@ -49,8 +42,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 //   float  part_dw[3][CT_GX][2][128][64], part_db[3][CT_GX][256], part_dwm[CT_MGX][128], part_dbm[CT_MGX][2]
 //   float  lse[3][N]
 #define CT_WS_DOUBLES (3 * CT_GX * 2 + CT_MGX)
-#define CT_WS_FLOATS ((int64_t)3 * CT_GX * CT_N * CT_K + 3 * CT_GX * CT_N + CT_MGX * 2 * CT_K + CT_MGX * 2)
+#define CT_WS_FLOATS ((int64_t)3 * CT_GX * CSS_N * CSS_K + 3 * CT_GX * CSS_N + CT_MGX * 2 * CSS_K + CT_MGX * 2)
 #define CT_WS_FIXED ((int64_t)CT_WS_DOUBLES * 8 + CT_WS_FLOATS * 4)
+static_assert(CT_WS_FIXED == SDFR_CSS_LOSS_WS_FIXED, "include/sdfr.h publishes the size of this layout: change both together");
 
 struct CssLossArgs {
     const float* x[3];             // x_u, x_v, x_w [B][64][HW]
@@ -70,70 +64,30 @@ struct CssLossArgs {
 
 __global__ __launch_bounds__(256, 2) void css_loss_fwd_kernel(CssLossArgs A) {
     extern __shared__ __align__(16) float smem[];
-    float* wT = smem;                              // [64][CT_LD]
-    float* bs = smem + CT_K * CT_LD;               // [256] bias
+    float* wT = smem;                              // [64][CSS_LD]
+    float* bs = smem + CSS_K * CSS_LD;             // [256] bias
     const int head = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 31, h = lane >> 5;
-    {
-        const float4* W4 = reinterpret_cast<const float4*>(A.w[head]);
-        for (int i = tid; i < CT_N * CT_K / 4; i += 256) {
-            const float4 v = W4[i];
-            const int c = i >> 4, k = (i & 15) * 4;
-            wT[(k + 0) * CT_LD + c] = v.x;
-            wT[(k + 1) * CT_LD + c] = v.y;
-            wT[(k + 2) * CT_LD + c] = v.z;
-            wT[(k + 3) * CT_LD + c] = v.w;
-        }
-        bs[tid] = A.b[head][tid];
-    }
+    css_stage_weights<CSS_N>(A.w[head], A.b[head], wT, bs, tid);
     __syncthreads();
 
     const int HW = A.HW;
     double lsum = 0.0, nfg = 0.0;
     for (int64_t tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
-        const int b = (int)(tile / A.tiles_per_crop);
-        const int pix = (int)(tile % A.tiles_per_crop) * CT_TILE + wave * 32 + col;
-        const bool live = pix < HW;
-        if (wave * 32 + (int)(tile % A.tiles_per_crop) * CT_TILE >= HW) continue;          // the whole wave is past the crop (wave-uniform)
-        const int p = live ? pix : 0;
+        const CssLane L = css_tile_lane(tile, A.tiles_per_crop, HW, wave, col);
+        if (L.wave_past_crop) continue;
+        const int b = L.b, pix = L.pix, p = L.p;
+        const bool live = L.live;
 
-        const float* xh = A.x[head] + ((int64_t)b * CT_K + h) * HW + p;
+        const float* xh = A.x[head] + ((int64_t)b * CSS_K + h) * HW + p;
         float xb[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) xb[s] = live ? xh[(int64_t)(2 * s) * HW] : 0.f;
+        css_prefetch8(xh, HW, live, xb);
         const bool m = live && A.mask[(int64_t)b * HW + p] != 0;
         const int tg = m ? (int)A.uvw[((int64_t)b * 3 + head) * HW + p] : 0;
 
-        // ---- logits: the forward's chain (8 tiles of 32 classes x 32 pixels, k in order, bias last)
+        // ---- logits: the function of the inference path (8 tiles of 32 classes x 32 pixels, k in order, bias last) and the maximum
         f32x16 acc[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-        const float* wa = wT + h * CT_LD + col;
-#pragma unroll 1
-        for (int g = 0; g < 4; ++g) {
-            float xn[8];
-#pragma unroll
-            for (int s = 0; s < 8; ++s) xn[s] = (live && g < 3) ? xh[(int64_t)(2 * (8 * (g + 1) + s)) * HW] : 0.f;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-#pragma unroll
-                for (int t = 0; t < 8; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[2 * (8 * g + s) * CT_LD + 32 * t], xb[s], acc[t], 0, 0, 0);
-            }
-#pragma unroll
-            for (int s = 0; s < 8; ++s) xb[s] = xn[s];
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                acc[t][r] = acc[t][r] + bs[CT_CLASS(t, r, h)];
-                mx = fmaxf(mx, acc[t][r]);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float mx = css_logits_tile(wT, bs, xh, HW, live, col, h, xb, acc);
 
         // ---- log-sum-exp (float64 sum, classes in register order, half 0 before half 1) and the target logit
         double s1 = 0.0;
@@ -143,10 +97,9 @@ __global__ __launch_bounds__(256, 2) void css_loss_fwd_kernel(CssLossArgs A) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 s1 += (double)expf(acc[t][r] - mx);
-                zt = (CT_CLASS(t, r, h) == tg) ? acc[t][r] : zt;
+                zt = (CSS_CLASS(t, r, h) == tg) ? acc[t][r] : zt;
             }
-        const double s1_o = __shfl_xor(s1, 32);
-        const float lse = mx + (float)log(h ? s1_o + s1 : s1 + s1_o);
+        const float lse = mx + (float)log(css_pair_sum(s1, h));
         const float zt_o = __shfl_xor(zt, 32);
         const float ztf = (((tg >> 2) & 1) == h) ? zt : zt_o;
         if (m && h == 0) {
@@ -161,7 +114,7 @@ __global__ __launch_bounds__(256, 2) void css_loss_fwd_kernel(CssLossArgs A) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float pr = expf(acc[t][r] - lse);
-                const float oh = (CT_CLASS(t, r, h) == tg) ? 1.f : 0.f;
+                const float oh = (CSS_CLASS(t, r, h) == tg) ? 1.f : 0.f;
                 acc[t][r] = m ? (pr - oh) * A.invN : 0.f;
             }
 
@@ -171,21 +124,21 @@ __global__ __launch_bounds__(256, 2) void css_loss_fwd_kernel(CssLossArgs A) {
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) dxa[mt][r] = 0.f;
-        const float* wd = wT + col * CT_LD + 4 * h;
+        const float* wd = wT + col * CSS_LD + 4 * h;
 #pragma unroll
         for (int t = 0; t < 8; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt)
-                    dxa[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wd[32 * mt * CT_LD + CT_CLASS(t, r, 0)], acc[t][r], dxa[mt], 0, 0, 0);
+                    dxa[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wd[32 * mt * CSS_LD + CSS_CLASS(t, r, 0)], acc[t][r], dxa[mt], 0, 0, 0);
             }
         if (live) {
-            float* d = A.dx[head] + ((int64_t)b * CT_K + 4 * h) * HW + pix;
+            float* d = A.dx[head] + ((int64_t)b * CSS_K + 4 * h) * HW + pix;
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) d[(int64_t)(32 * mt + CT_ROW(r, 0)) * HW] = dxa[mt][r];
+                for (int r = 0; r < 16; ++r) d[(int64_t)(32 * mt + CSS_ROW(r, 0)) * HW] = dxa[mt][r];
         }
     }
 
@@ -194,14 +147,7 @@ __global__ __launch_bounds__(256, 2) void css_loss_fwd_kernel(CssLossArgs A) {
     double* red = reinterpret_cast<double*>(smem);
     red[tid] = lsum;
     red[256 + tid] = nfg;
-    __syncthreads();
-    for (int n = 128; n > 0; n >>= 1) {
-        if (tid < n) {
-            red[tid] += red[tid + n];
-            red[256 + tid] += red[256 + tid + n];
-        }
-        __syncthreads();
-    }
+    css_tree_sum256<2>(red, tid);
     if (tid == 0) {
         double* o = A.part_loss + ((int64_t)head * gridDim.x + blockIdx.x) * 2;
         o[0] = red[0];
@@ -213,25 +159,14 @@ __global__ __launch_bounds__(256, 2) void css_loss_fwd_kernel(CssLossArgs A) {
 __global__ __launch_bounds__(256, 2) void css_loss_dw_kernel(CssLossArgs A) {
     extern __shared__ __align__(16) float smem[];
     float* wT = smem;                              // [64][CT_LDH]: W^T of the workgroup's 128 classes
-    float* bs = wT + CT_K * CT_LDH;                // [128]
+    float* bs = wT + CSS_K * CT_LDH;               // [128]
     float* xs = bs + 128;                          // [4 waves][64][CT_XP]
-    float* pl = xs + 4 * CT_K * CT_XP;             // [4][32] lse, then [4][32] scale, then [4][32] target (int)
+    float* pl = xs + 4 * CSS_K * CT_XP;            // [4][32] lse, then [4][32] scale, then [4][32] target (int)
     float* ps = pl + 128;
     int* pt = reinterpret_cast<int*>(ps + 128);
     const int head = blockIdx.y, zh = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 31, h = lane >> 5;
-    {
-        const float4* W4 = reinterpret_cast<const float4*>(A.w[head]) + zh * 128 * (CT_K / 4);
-        for (int i = tid; i < 128 * CT_K / 4; i += 256) {
-            const float4 v = W4[i];
-            const int c = i >> 4, k = (i & 15) * 4;
-            wT[(k + 0) * CT_LDH + c] = v.x;
-            wT[(k + 1) * CT_LDH + c] = v.y;
-            wT[(k + 2) * CT_LDH + c] = v.z;
-            wT[(k + 3) * CT_LDH + c] = v.w;
-        }
-        if (tid < 128) bs[tid] = A.b[head][zh * 128 + tid];
-    }
+    css_stage_weights<CT_NH>(A.w[head] + zh * CT_NH * CSS_K, A.b[head] + zh * CT_NH, wT, bs, tid);      // (the loop's first barrier follows)
     const int HW = A.HW;
     f32x16 dw[4][2];
     float dbacc[4];
@@ -243,15 +178,14 @@ __global__ __launch_bounds__(256, 2) void css_loss_dw_kernel(CssLossArgs A) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) dw[t][nt][r] = 0.f;
     }
-    float* xsw = xs + wave * CT_K * CT_XP;
+    float* xsw = xs + wave * CSS_K * CT_XP;
     for (int64_t tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {                 // the same trips for every wave: barriers inside
-        const int b = (int)(tile / A.tiles_per_crop);
-        const int pix = (int)(tile % A.tiles_per_crop) * CT_TILE + wave * 32 + col;
-        const bool live = pix < HW;
-        const int p = live ? pix : 0;
+        const CssLane L = css_tile_lane(tile, A.tiles_per_crop, HW, wave, col);            // (no early-out on L.wave_past_crop: barriers)
+        const int b = L.b, p = L.p;
+        const bool live = L.live;
         __syncthreads();                                                                   // the previous tile's LDS reads are done
         {
-            const float* xh = A.x[head] + ((int64_t)b * CT_K + h) * HW + p;
+            const float* xh = A.x[head] + ((int64_t)b * CSS_K + h) * HW + p;
 #pragma unroll 8
             for (int s = 0; s < 32; ++s) xsw[(2 * s + h) * CT_XP + col] = live ? xh[(int64_t)(2 * s) * HW] : 0.f;
             if (h == 0) {
@@ -262,12 +196,12 @@ __global__ __launch_bounds__(256, 2) void css_loss_dw_kernel(CssLossArgs A) {
             }
         }
         __syncthreads();
-        const float* plw = pl + wave * 32 + 4 * h;                                         // per-pixel data of register r: index CT_ROW(r, 0)
+        const float* plw = pl + wave * 32 + 4 * h;                                         // per-pixel data of register r: index CSS_ROW(r, 0)
         const float* psw = ps + wave * 32 + 4 * h;
         const int* ptw = pt + wave * 32 + 4 * h;
         bool any = false;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) any = any || psw[CT_ROW(r, 0)] != 0.f;
+        for (int r = 0; r < 16; ++r) any = any || psw[CSS_ROW(r, 0)] != 0.f;
         if (__builtin_amdgcn_ballot_w64(any) == 0ull) continue;                            // no foreground pixel in the wave's 32: g is all zero
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -283,19 +217,18 @@ __global__ __launch_bounds__(256, 2) void css_loss_dw_kernel(CssLossArgs A) {
             float dbs = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float pr = expf((z[r] + bias) - plw[CT_ROW(r, 0)]);
-                const float g = (pr - (ptw[CT_ROW(r, 0)] == cls ? 1.f : 0.f)) * psw[CT_ROW(r, 0)];
+                const float pr = expf((z[r] + bias) - plw[CSS_ROW(r, 0)]);
+                const float g = (pr - (ptw[CSS_ROW(r, 0)] == cls ? 1.f : 0.f)) * psw[CSS_ROW(r, 0)];
                 z[r] = g;
                 dbs += g;
             }
-            const float dbs_o = __shfl_xor(dbs, 32);
-            dbacc[t] += h ? dbs_o + dbs : dbs + dbs_o;
+            dbacc[t] += css_pair_sum(dbs, h);
             // dW[class][k] += sum over the 32 pixels: A = g (lane = class, slots = pixels ROW(r, 0 / 1)), B = x[32 nt + col][that pixel]
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt)
-                    dw[t][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(z[r], xsw[(32 * nt + col) * CT_XP + CT_ROW(r, h)], dw[t][nt], 0, 0, 0);
+                    dw[t][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(z[r], xsw[(32 * nt + col) * CT_XP + CSS_ROW(r, h)], dw[t][nt], 0, 0, 0);
             }
         }
     }
@@ -329,15 +262,15 @@ __global__ __launch_bounds__(256, 2) void css_loss_dw_kernel(CssLossArgs A) {
     __syncthreads();
     const int64_t blk = (int64_t)head * gridDim.x + blockIdx.x;
     if (wave == 0) {
-        float* o = A.part_dw + (blk * 2 + zh) * 128 * CT_K;
+        float* o = A.part_dw + (blk * 2 + zh) * 128 * CSS_K;
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) o[(32 * t + CT_ROW(r, h)) * CT_K + 32 * nt + col] = dw[t][nt][r];
+                for (int r = 0; r < 16; ++r) o[(32 * t + CSS_ROW(r, h)) * CSS_K + 32 * nt + col] = dw[t][nt][r];
     }
-    if (tid < 128) A.part_db[blk * CT_N + zh * 128 + tid] = ((smem[tid] + smem[128 + tid]) + smem[256 + tid]) + smem[384 + tid];
+    if (tid < 128) A.part_db[blk * CSS_N + zh * 128 + tid] = ((smem[tid] + smem[128 + tid]) + smem[256 + tid]) + smem[384 + tid];
 }
 
 // ---- mask head: 64 -> 2 on fmaf chains, a thread per pixel ------------------------------------------------------------------------------------
@@ -357,12 +290,12 @@ struct CssMaskLossArgs {
 
 __global__ __launch_bounds__(256) void css_loss_mask_kernel(CssMaskLossArgs A) {
     extern __shared__ __align__(16) float smem[];
-    float* xs = smem;                              // [64][CT_LD]: the tile's features, [k][pixel]
-    float* gs = xs + CT_K * CT_LD;                 // [2][256]: the tile's logit gradients
+    float* xs = smem;                              // [64][CT_MLD]: the tile's features, [k][pixel]
+    float* gs = xs + CSS_K * CT_MLD;               // [2][256]: the tile's logit gradients
     float* ws = gs + 2 * CT_MTILE;                 // [128] weights, [2] bias
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < 2 * CT_K) ws[tid] = A.wm[tid];
-    if (tid < 2) ws[2 * CT_K + tid] = A.bm[tid];
+    if (tid < 2 * CSS_K) ws[tid] = A.wm[tid];
+    if (tid < 2) ws[2 * CSS_K + tid] = A.bm[tid];
     __syncthreads();
     const int HW = A.HW;
     const int half = tid >> 7, c = (tid >> 6) & 1, k = tid & 63;       // the dW role of the thread: pixels 128 half ... + 127 of the tile
@@ -374,17 +307,17 @@ __global__ __launch_bounds__(256) void css_loss_mask_kernel(CssMaskLossArgs A) {
         const bool live = pix < HW;
         const int p = live ? pix : 0;
         __syncthreads();
-        const float* xm = A.xm + (int64_t)b * CT_K * HW + p;
+        const float* xm = A.xm + (int64_t)b * CSS_K * HW + p;
         float m0 = 0.f, m1 = 0.f;
 #pragma unroll 16
-        for (int j = 0; j < CT_K; ++j) {
+        for (int j = 0; j < CSS_K; ++j) {
             const float v = live ? xm[(int64_t)j * HW] : 0.f;
-            xs[j * CT_LD + tid] = v;
+            xs[j * CT_MLD + tid] = v;
             m0 = fmaf(ws[j], v, m0);
-            m1 = fmaf(ws[CT_K + j], v, m1);
+            m1 = fmaf(ws[CSS_K + j], v, m1);
         }
-        m0 = m0 + ws[2 * CT_K];
-        m1 = m1 + ws[2 * CT_K + 1];
+        m0 = m0 + ws[2 * CSS_K];
+        m1 = m1 + ws[2 * CSS_K + 1];
         const bool fg = live && A.mask[(int64_t)b * HW + p] != 0;
         const float mm = fmaxf(m0, m1);
         const float e0 = expf(m0 - mm), e1 = expf(m1 - mm), S = e0 + e1;
@@ -394,13 +327,13 @@ __global__ __launch_bounds__(256) void css_loss_mask_kernel(CssMaskLossArgs A) {
         gs[tid] = g0;
         gs[CT_MTILE + tid] = g1;
         if (live) {
-            float* d = A.dxm + (int64_t)b * CT_K * HW + pix;
+            float* d = A.dxm + (int64_t)b * CSS_K * HW + pix;
 #pragma unroll 16
-            for (int j = 0; j < CT_K; ++j) d[(int64_t)j * HW] = fmaf(ws[CT_K + j], g1, ws[j] * g0);
+            for (int j = 0; j < CSS_K; ++j) d[(int64_t)j * HW] = fmaf(ws[CSS_K + j], g1, ws[j] * g0);
         }
         __syncthreads();
         const float* gp = gs + c * CT_MTILE + half * 128;
-        const float* xp = xs + k * CT_LD + half * 128;
+        const float* xp = xs + k * CT_MLD + half * 128;
 #pragma unroll 16
         for (int i = 0; i < 128; ++i) dwa = fmaf(gp[i], xp[i], dwa);
         if (wave < 2) {                                                // db of class `wave`: four strided terms, then a fixed shuffle tree
@@ -416,11 +349,7 @@ __global__ __launch_bounds__(256) void css_loss_mask_kernel(CssMaskLossArgs A) {
     float* dwh = smem + 512;
     red[tid] = lsum;
     dwh[tid] = dwa;
-    __syncthreads();
-    for (int n = 128; n > 0; n >>= 1) {
-        if (tid < n) red[tid] += red[tid + n];
-        __syncthreads();
-    }
+    css_tree_sum256<1>(red, tid);
     if (tid == 0) A.part_loss[blockIdx.x] = red[0];
     if (tid < 128) A.part_dw[(int64_t)blockIdx.x * 128 + tid] = dwh[tid] + dwh[128 + tid];
     if (wave < 2 && lane == 0) A.part_db[(int64_t)blockIdx.x * 2 + wave] = dba;
@@ -442,37 +371,37 @@ struct CssReduceArgs {
     int64_t N;
 };
 
-#define CT_RED_DW (3 * CT_N * CT_K)
-#define CT_RED_DB (3 * CT_N)
-#define CT_RED_TOTAL (CT_RED_DW + CT_RED_DB + 2 * CT_K + 2 + 4)
+#define CT_RED_DW (3 * CSS_N * CSS_K)
+#define CT_RED_DB (3 * CSS_N)
+#define CT_RED_TOTAL (CT_RED_DW + CT_RED_DB + 2 * CSS_K + 2 + 4)
 
 __global__ __launch_bounds__(256) void css_loss_reduce_kernel(CssReduceArgs A) {
     int e = blockIdx.x * 256 + threadIdx.x;
     if (e < CT_RED_DW) {
-        const int head = e / (CT_N * CT_K), i = e % (CT_N * CT_K);
-        const float* p = A.part_dw + (int64_t)head * A.gx * CT_N * CT_K + i;
+        const int head = e / (CSS_N * CSS_K), i = e % (CSS_N * CSS_K);
+        const float* p = A.part_dw + (int64_t)head * A.gx * CSS_N * CSS_K + i;
         float s = 0.f;
-        for (int g = 0; g < A.gx; ++g) s += p[(int64_t)g * CT_N * CT_K];
+        for (int g = 0; g < A.gx; ++g) s += p[(int64_t)g * CSS_N * CSS_K];
         A.dw[head][i] = s;
         return;
     }
     e -= CT_RED_DW;
     if (e < CT_RED_DB) {
-        const int head = e / CT_N, i = e % CT_N;
-        const float* p = A.part_db + (int64_t)head * A.gx * CT_N + i;
+        const int head = e / CSS_N, i = e % CSS_N;
+        const float* p = A.part_db + (int64_t)head * A.gx * CSS_N + i;
         float s = 0.f;
-        for (int g = 0; g < A.gx; ++g) s += p[(int64_t)g * CT_N];
+        for (int g = 0; g < A.gx; ++g) s += p[(int64_t)g * CSS_N];
         A.db[head][i] = s;
         return;
     }
     e -= CT_RED_DB;
-    if (e < 2 * CT_K) {
+    if (e < 2 * CSS_K) {
         float s = 0.f;
         for (int g = 0; g < A.gm; ++g) s += A.part_dwm[(int64_t)g * 128 + e];
         A.dwm[e] = s;
         return;
     }
-    e -= 2 * CT_K;
+    e -= 2 * CSS_K;
     if (e < 2) {
         float s = 0.f;
         for (int g = 0; g < A.gm; ++g) s += A.part_dbm[(int64_t)g * 2 + e];
@@ -558,15 +487,6 @@ __global__ __launch_bounds__(256) void css_latent_reduce_kernel(const float* __r
     }
 }
 
-static int css_train_device_check(const void* p, const char* what) {
-    int cur = -1;
-    SDFR_HIP_CHECK(hipGetDevice(&cur));
-    hipPointerAttribute_t at;
-    SDFR_HIP_CHECK(hipPointerGetAttributes(&at, p));
-    SDFR_REQUIRE(at.device == cur, "%s: the tensors live on device %d but the current device (the launch stream's) is %d", what, at.device, cur);
-    return SDFR_OK;
-}
-
 extern "C" int sdfr_css_head_loss(const float* x_u, const float* x_v, const float* x_w, const float* x_mask, int B, int C, int H, int W,
                                   const float* w_u, const float* b_u, const float* w_v, const float* b_v, const float* w_w, const float* b_w,
                                   const float* w_mask, const float* b_mask, const uint8_t* uvw_gt, const uint8_t* mask_gt, float* loss,
@@ -574,7 +494,7 @@ extern "C" int sdfr_css_head_loss(const float* x_u, const float* x_v, const floa
                                   float* dw_w, float* db_w, float* dw_mask, float* db_mask, void* workspace, int64_t workspace_bytes,
                                   void* stream) {
     SDFR_REQUIRE(B >= 0 && H >= 0 && W >= 0, "sdfr_css_head_loss: negative size");
-    SDFR_REQUIRE(C == CT_K, "sdfr_css_head_loss: the head takes %d feature channels (got %d)", CT_K, C);
+    SDFR_REQUIRE(C == CSS_K, "sdfr_css_head_loss: the head takes %d feature channels (got %d)", CSS_K, C);
     SDFR_REQUIRE((int64_t)H * W < (1ll << 30), "sdfr_css_head_loss: H * W = %lld is beyond 2^30", (long long)H * W);
     if (B == 0 || H == 0 || W == 0) return SDFR_OK;
     SDFR_REQUIRE(x_u && x_v && x_w && x_mask && w_u && b_u && w_v && b_v && w_w && b_w && w_mask && b_mask && uvw_gt && mask_gt,
@@ -586,16 +506,16 @@ extern "C" int sdfr_css_head_loss(const float* x_u, const float* x_v, const floa
     const int64_t need = CT_WS_FIXED + 3 * N * 4;
     SDFR_REQUIRE(workspace != nullptr && workspace_bytes >= need, "sdfr_css_head_loss: the workspace needs %lld bytes (%lld + 12 per pixel), got %lld",
                  (long long)need, (long long)CT_WS_FIXED, (long long)(workspace ? workspace_bytes : 0));
-    if (int rc = css_train_device_check(x_u, "sdfr_css_head_loss")) return rc;
+    if (int rc = css_device_check(x_u, "sdfr_css_head_loss")) return rc;
 
     double* wd = reinterpret_cast<double*>(workspace);
     double* part_loss = wd;
     double* part_lossm = wd + 3 * CT_GX * 2;
     float* wf = reinterpret_cast<float*>(wd + CT_WS_DOUBLES);
     float* part_dw = wf;
-    float* part_db = part_dw + (int64_t)3 * CT_GX * CT_N * CT_K;
-    float* part_dwm = part_db + 3 * CT_GX * CT_N;
-    float* part_dbm = part_dwm + CT_MGX * 2 * CT_K;
+    float* part_db = part_dw + (int64_t)3 * CT_GX * CSS_N * CSS_K;
+    float* part_dwm = part_db + 3 * CT_GX * CSS_N;
+    float* part_dbm = part_dwm + CT_MGX * 2 * CSS_K;
     float* lse = part_dbm + CT_MGX * 2;
 
     CssLossArgs A;
@@ -605,7 +525,7 @@ extern "C" int sdfr_css_head_loss(const float* x_u, const float* x_v, const floa
     A.dx[0] = dx_u; A.dx[1] = dx_v; A.dx[2] = dx_w;
     A.lse = lse; A.part_loss = part_loss; A.part_dw = part_dw; A.part_db = part_db;
     A.HW = HW;
-    A.tiles_per_crop = sdfr_cdiv(HW, CT_TILE);
+    A.tiles_per_crop = sdfr_cdiv(HW, CSS_TILE);
     A.n_tiles = (int64_t)B * A.tiles_per_crop;
     A.N = N;
     A.invN = (float)(1.0 / (double)N);
@@ -620,9 +540,9 @@ extern "C" int sdfr_css_head_loss(const float* x_u, const float* x_v, const floa
     M.invN = A.invN;
     const int gm = (int)(M.n_tiles < CT_MGX ? M.n_tiles : CT_MGX);
 
-    const size_t lds_fwd = (size_t)(CT_K * CT_LD + CT_N) * sizeof(float);
-    const size_t lds_dw = (size_t)(CT_K * CT_LDH + 128 + 4 * CT_K * CT_XP + 3 * 128) * sizeof(float);
-    const size_t lds_mask = (size_t)(CT_K * CT_LD + 2 * CT_MTILE + 2 * CT_K + 2) * sizeof(float);
+    const size_t lds_fwd = (size_t)(CSS_K * CSS_LD + CSS_N) * sizeof(float);
+    const size_t lds_dw = (size_t)(CSS_K * CT_LDH + 128 + 4 * CSS_K * CT_XP + 3 * 128) * sizeof(float);
+    const size_t lds_mask = (size_t)(CSS_K * CT_MLD + 2 * CT_MTILE + 2 * CSS_K + 2) * sizeof(float);
     // (more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device's image of the kernel, so it is set at every call)
     SDFR_HIP_CHECK(hipFuncSetAttribute((const void*)css_loss_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fwd));
     SDFR_HIP_CHECK(hipFuncSetAttribute((const void*)css_loss_dw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dw));
@@ -654,7 +574,7 @@ extern "C" int sdfr_css_latent_loss(const float* x4, int B, int C, int h, int w,
     const int64_t need = (int64_t)B * (8 + CTL_PART * 4);
     SDFR_REQUIRE(workspace != nullptr && workspace_bytes >= need, "sdfr_css_latent_loss: the workspace needs %lld bytes (%d per crop), got %lld",
                  (long long)need, 8 + CTL_PART * 4, (long long)(workspace ? workspace_bytes : 0));
-    if (int rc = css_train_device_check(x4, "sdfr_css_latent_loss")) return rc;
+    if (int rc = css_device_check(x4, "sdfr_css_latent_loss")) return rc;
     double* part_loss = reinterpret_cast<double*>(workspace);
     float* part = reinterpret_cast<float*>(part_loss + B);
     hipLaunchKernelGGL(css_latent_loss_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x4, w_lat, b_lat, latent_gt, h * w, B, dx4, part,

@@ -11,9 +11,12 @@ from . import _lib
 from ._lib import SdfrError, check, guard, lib, ptr, stream_ptr
 
 N_FEAT, N_CLASS, N_LAT_FEAT = 64, 256, 256
-# css_head_loss's workspace: the workgroups' partial dW / db / loss sums (a fixed grid: 80 workgroups per colour head, 128 for the mask head;
-# include/sdfr.h SDFR_CSS_LOSS_WS_FIXED) plus one float32 log-sum-exp per pixel and colour head.  Nothing else is allocated besides the outputs.
-HEAD_LOSS_WORKSPACE_FIXED_BYTES = (3 * 80 * 2 + 128) * 8 + (3 * 80 * 256 * 64 + 3 * 80 * 256 + 128 * 128 + 128 * 2) * 4
+# css_head_loss's workspace: the workgroups' partial dW / db / loss sums on a fixed grid (csrc/css_train.hip: CT_GX workgroups per colour head,
+# CT_MGX for the mask head; include/sdfr.h SDFR_CSS_LOSS_WS_FIXED) plus one float32 log-sum-exp per pixel and colour head.  Nothing else is
+# allocated besides the outputs.
+_GX, _MGX = 80, 128
+HEAD_LOSS_WORKSPACE_FIXED_BYTES = ((3 * _GX * 2 + _MGX) * 8
+                                   + (3 * _GX * N_CLASS * N_FEAT + 3 * _GX * N_CLASS + _MGX * 2 * N_FEAT + _MGX * 2) * 4)
 HEAD_LOSS_WORKSPACE_BYTES_PER_PIXEL = 12
 LATENT_LOSS_WORKSPACE_BYTES_PER_CROP = 8 + (3 * 256 + 3) * 4
 
@@ -50,6 +53,40 @@ def _linear(wb, what, n_out, n_in, device):
     return w.to(device).contiguous(), b.to(device).contiguous()
 
 
+_HEADS = ('u', 'v', 'w', 'mask')
+
+
+def _head_inputs(fn, x_u, x_v, x_w, x_mask, weights):
+    """what css_head and head_loss_raw (`fn`: the caller's name in the messages) check alike: B, C, H, W, the device, the four features and
+    the (weight, bias) pairs of u, v, w, mask"""
+    x_u = _f32_cuda(x_u, "%s: x_u" % fn)
+    if x_u.dim() != 4:
+        raise SdfrError("%s: x_u must be [B][64][H][W] (got shape %s)" % (fn, tuple(x_u.shape)))
+    B, C, H, W = (int(v) for v in x_u.shape)
+    x_v = _f32_cuda(x_v, "%s: x_v" % fn, x_u.shape)
+    x_w = _f32_cuda(x_w, "%s: x_w" % fn, x_u.shape)
+    x_mask = _f32_cuda(x_mask, "%s: x_mask" % fn, x_u.shape)
+    dev = x_u.device
+    for t, n in ((x_v, "x_v"), (x_w, "x_w"), (x_mask, "x_mask")):
+        if t.device != dev:
+            raise SdfrError("%s: %s lives on %s, x_u on %s" % (fn, n, t.device, dev))
+    if C != N_FEAT:
+        raise SdfrError("%s: the head takes %d feature channels (got %d)" % (fn, N_FEAT, C))
+    wb = [_linear(weights[h], "%s: weights['%s']" % (fn, h), 2 if h == 'mask' else N_CLASS, N_FEAT, dev) for h in _HEADS]
+    return B, C, H, W, dev, (x_u, x_v, x_w, x_mask), wb
+
+
+def _latent_inputs(fn, x4, w, b):
+    """what css_latent and latent_loss_raw check alike: B, C, h, w, the feature map and out_lat's (weight, bias)"""
+    x4 = _f32_cuda(x4, "%s: x4" % fn)
+    if x4.dim() != 4:
+        raise SdfrError("%s: x4 must be [B][256][h][w] (got shape %s)" % (fn, tuple(x4.shape)))
+    B, C, h, wd = (int(v) for v in x4.shape)
+    if C != N_LAT_FEAT:
+        raise SdfrError("%s: out_lat takes %d feature channels (got %d)" % (fn, N_LAT_FEAT, C))
+    return B, C, h, wd, x4, _linear((w, b), "%s: out_lat" % fn, 3, N_LAT_FEAT, x4.device)
+
+
 @_lib.traced("css_head")
 def css_head(x_u, x_v, x_w, x_mask, weights, logprobs=False):
     """The fused output head.  x_u, x_v, x_w, x_mask: contiguous float32 GPU tensors [B][64][H][W] (the outputs of up4_u / up4_v / up4_w /
@@ -61,23 +98,7 @@ def css_head(x_u, x_v, x_w, x_mask, weights, logprobs=False):
       'mask_sm' [B][1][H][W]        softmax(100 mask)[1]
       'u', 'v', 'w' [B][256][H][W]  log_softmax(logit), only with logprobs=True
     A crop's result does not depend on the batch it is computed in.  Anything but float32, 64 channels and contiguous NCHW is refused."""
-    x_u = _f32_cuda(x_u, "css_head: x_u")
-    if x_u.dim() != 4:
-        raise SdfrError("css_head: x_u must be [B][64][H][W] (got shape %s)" % (tuple(x_u.shape),))
-    B, C, H, W = (int(v) for v in x_u.shape)
-    x_v = _f32_cuda(x_v, "css_head: x_v", x_u.shape)
-    x_w = _f32_cuda(x_w, "css_head: x_w", x_u.shape)
-    x_mask = _f32_cuda(x_mask, "css_head: x_mask", x_u.shape)
-    dev = x_u.device
-    for t, n in ((x_v, "x_v"), (x_w, "x_w"), (x_mask, "x_mask")):
-        if t.device != dev:
-            raise SdfrError("css_head: %s lives on %s, x_u on %s" % (n, t.device, dev))
-    if C != N_FEAT:
-        raise SdfrError("css_head: the head takes %d feature channels (got %d)" % (N_FEAT, C))
-    wu, bu = _linear(weights['u'], "css_head: weights['u']", N_CLASS, N_FEAT, dev)
-    wv, bv = _linear(weights['v'], "css_head: weights['v']", N_CLASS, N_FEAT, dev)
-    ww, bw = _linear(weights['w'], "css_head: weights['w']", N_CLASS, N_FEAT, dev)
-    wm, bm = _linear(weights['mask'], "css_head: weights['mask']", 2, N_FEAT, dev)
+    B, C, H, W, dev, (x_u, x_v, x_w, x_mask), ((wu, bu), (wv, bv), (ww, bw), (wm, bm)) = _head_inputs("css_head", x_u, x_v, x_w, x_mask, weights)
     new = lambda c: torch.empty((B, c, H, W), dtype=torch.float32, device=dev)       # noqa: E731
     out = {'uvw_sm': new(3), 'uvw_sm_masked': new(3), 'mask': new(2), 'mask_sm': new(1)}
     if logprobs:
@@ -93,13 +114,7 @@ def css_head(x_u, x_v, x_w, x_mask, weights, logprobs=False):
 def css_latent(x4, w, b):
     """out_lat of the reference on x4 [B][256][h][w] (contiguous float32, GPU): the 1x1 convolution w [3][256] (or [3][256][1][1]), b [3], the
     mean over the pixels and the projection onto the unit sphere, v * (1 / (|v| + 1e-8)).  Returns a new, detached [B][3] tensor."""
-    x4 = _f32_cuda(x4, "css_latent: x4")
-    if x4.dim() != 4:
-        raise SdfrError("css_latent: x4 must be [B][256][h][w] (got shape %s)" % (tuple(x4.shape),))
-    B, C, h, wd = (int(v) for v in x4.shape)
-    if C != N_LAT_FEAT:
-        raise SdfrError("css_latent: out_lat takes %d feature channels (got %d)" % (N_LAT_FEAT, C))
-    wl, bl = _linear((w, b), "css_latent: out_lat", 3, N_LAT_FEAT, x4.device)
+    B, C, h, wd, x4, (wl, bl) = _latent_inputs("css_latent", x4, w, b)
     out = torch.empty((B, 3), dtype=torch.float32, device=x4.device)
     with guard(x4):
         check(lib().sdfr_css_latent(ptr(x4), B, C, h, wd, ptr(wl), ptr(bl), ptr(out), stream_ptr()), "sdfr_css_latent")
@@ -134,20 +149,8 @@ def head_loss_raw(x_u, x_v, x_w, x_mask, weights, uvw_gt, mask_gt):
     """The fused call behind css_head_loss, without autograd: returns {'loss': float32 [4] (u, v, w, mask), 'dx': {'u', 'v', 'w', 'mask'}
     [B][64][H][W], 'dw': {...} [256][64] ([2][64] for the mask), 'db': {...}}, the gradients of each head's own loss for unit upstream gradient.
     Allocates head_loss_workspace_bytes(B, H, W) besides what it returns."""
-    x_u = _f32_cuda(x_u, "css_head_loss: x_u")
-    if x_u.dim() != 4:
-        raise SdfrError("css_head_loss: x_u must be [B][64][H][W] (got shape %s)" % (tuple(x_u.shape),))
-    B, C, H, W = (int(v) for v in x_u.shape)
-    x_v = _f32_cuda(x_v, "css_head_loss: x_v", x_u.shape)
-    x_w = _f32_cuda(x_w, "css_head_loss: x_w", x_u.shape)
-    x_mask = _f32_cuda(x_mask, "css_head_loss: x_mask", x_u.shape)
-    dev = x_u.device
-    for t, n in ((x_v, "x_v"), (x_w, "x_w"), (x_mask, "x_mask")):
-        if t.device != dev:
-            raise SdfrError("css_head_loss: %s lives on %s, x_u on %s" % (n, t.device, dev))
-    if C != N_FEAT:
-        raise SdfrError("css_head_loss: the head takes %d feature channels (got %d)" % (N_FEAT, C))
-    wb = {h: _linear(weights[h], "css_head_loss: weights['%s']" % h, 2 if h == 'mask' else N_CLASS, N_FEAT, dev) for h in ('u', 'v', 'w', 'mask')}
+    B, C, H, W, dev, (x_u, x_v, x_w, x_mask), wb = _head_inputs("css_head_loss", x_u, x_v, x_w, x_mask, weights)
+    wb = dict(zip(_HEADS, wb))
     uvw = _target_u8(uvw_gt, "css_head_loss: uvw_gt", (B, 3, H, W), dev)
     msk = _target_u8(mask_gt, "css_head_loss: mask_gt", (B, H, W), dev)
     f = lambda *shape: _new(shape, dev, B * H * W == 0)                                # noqa: E731
@@ -166,13 +169,7 @@ def head_loss_raw(x_u, x_v, x_w, x_mask, weights, uvw_gt, mask_gt):
 
 def latent_loss_raw(x4, w, b, latent_gt):
     """The fused call behind css_latent_loss: {'loss': float32 [1], 'dx': [B][256][h][w], 'dw': [3][256], 'db': [3]} for unit upstream gradient"""
-    x4 = _f32_cuda(x4, "css_latent_loss: x4")
-    if x4.dim() != 4:
-        raise SdfrError("css_latent_loss: x4 must be [B][256][h][w] (got shape %s)" % (tuple(x4.shape),))
-    B, C, h, wd = (int(v) for v in x4.shape)
-    if C != N_LAT_FEAT:
-        raise SdfrError("css_latent_loss: out_lat takes %d feature channels (got %d)" % (N_LAT_FEAT, C))
-    wl, bl = _linear((w, b), "css_latent_loss: out_lat", 3, N_LAT_FEAT, x4.device)
+    B, C, h, wd, x4, (wl, bl) = _latent_inputs("css_latent_loss", x4, w, b)
     gt = _f32_cuda(latent_gt, "css_latent_loss: latent_gt", (B, 3))
     if gt.device != x4.device:
         raise SdfrError("css_latent_loss: latent_gt lives on %s, x4 on %s" % (gt.device, x4.device))
@@ -184,9 +181,6 @@ def latent_loss_raw(x4, w, b, latent_gt):
         check(lib().sdfr_css_latent_loss(ptr(x4), B, C, h, wd, ptr(wl), ptr(bl), ptr(gt), ptr(out['loss']), ptr(out['dx']), ptr(out['dw']),
                                          ptr(out['db']), ptr(ws), ws_bytes, stream_ptr()), "sdfr_css_latent_loss")
     return out
-
-
-_HEADS = ('u', 'v', 'w', 'mask')
 
 
 class _HeadLoss(torch.autograd.Function):
