@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 408        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 409        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -42,7 +42,7 @@ extern "C" {
  * sdfr_image_box_iou; 403: the evaluator's statistics sdfr_eval_*; 404: frame labelling, sdfr_reproject and
  * sdfr_point_extents; 405: frame ingest, sdfr_depth_map, sdfr_match_boxes and sdfr_css_input; 406: the CSS output head, sdfr_css_head and
  * sdfr_css_latent; 407: its training losses and gradients, sdfr_css_head_loss and sdfr_css_latent_loss; 408: the road-plane removal, sdfr_lidar_normals_ws_bytes,
- * sdfr_lidar_normals and sdfr_depth_map_masked).  A caller built
+ * sdfr_lidar_normals and sdfr_depth_map_masked; 409: the training-crop augmentation, sdfr_augment).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -794,6 +794,34 @@ int sdfr_match_boxes(const double* anno, int A, const double* det, int M, int32_
  *   Workspaces: coef int32[A][2][128][2 + ksize], tmp uint8[total rows][128][3].  Three launches. */
 int sdfr_css_input(const float* image, int H, int W, const int32_t* meta, int A, const float* masks, int ksize, int n_hblocks,
                    int32_t* coef, uint8_t* tmp, float* im, float* im_orig, uint8_t* u8, void* stream);
+
+/* Augmentation of a ragged batch of B training crops (csrc/augment.hip): what datasets/crops.py asks of Pillow through torchvision's PIL
+ * backend -- ColorJitter in a given order, rotate(angle, expand=True), resize to 128 x 128, crop((j, i, j + w, i + h)), resize to 128 x 128,
+ * ToTensor / Normalize; bilinear for the RGB image, nearest for the UVW label image -- byte for byte for the given parameters.
+ *   rgb_src, uvw_src: the uint8 [h_b][w_b][3] images of all samples, one behind the other (device memory, the same layout for both).
+ *   meta int32[B][8] = { h, w, index of the sample's first pixel in the packed sources, width and height of the rotated image
+ *   (Image.rotate's expanded size), 1 when angle % 360 == 0 (Pillow copies), 0, 0 }.
+ *   params float64[B][SDFR_AUG_PARAMS]: the factors Image.blend receives for brightness, contrast and saturation; the hue factor (0 skips
+ *   the step); the four operation ids (0 brightness, 1 contrast, 2 saturation, 3 hue) in the order applied; the six entries of
+ *   Image.rotate's re-centred affine matrix (host float64 arithmetic); the crop box i (top), j (left), h, w inside the intermediate.
+ *   ksize >= 2 * ceil(max(largest rotated extent / 128, 1)) + 1.
+ *   Workspaces: tab int32[B][4][128][3 + ksize], jit uint8[source pixels][3], mid_rgb and mid_uvw uint8[B][128][128][3].
+ *   Outputs: rgb float[B][3][128][128], uvw uint8[B][3][128][128], mask uint8[B][128][128] = (u + v + w > 0); rgb_u8 uint8[B][128][128][3],
+ *   the image before ToTensor, may be NULL.  After the call jit holds the images after the colour jitter.
+ *   Four launches whatever B; no atomics; a sample's results depend on its own rows alone. */
+#define SDFR_AUG_PARAMS 20
+#define SDFR_AUG_BRIGHTNESS 0
+#define SDFR_AUG_CONTRAST 1
+#define SDFR_AUG_SATURATION 2
+#define SDFR_AUG_HUE 3
+#define SDFR_AUG_ORDER 4
+#define SDFR_AUG_MATRIX 8
+#define SDFR_AUG_BOX_I 14
+#define SDFR_AUG_BOX_J 15
+#define SDFR_AUG_BOX_H 16
+#define SDFR_AUG_BOX_W 17
+int sdfr_augment(const uint8_t* rgb_src, const uint8_t* uvw_src, const int32_t* meta, const double* params, int B, int ksize, int32_t* tab,
+                 uint8_t* jit, uint8_t* mid_rgb, uint8_t* mid_uvw, float* rgb, uint8_t* uvw, uint8_t* mask, uint8_t* rgb_u8, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Lidar normals (csrc/normals.hip): the normal estimation behind get_kitti_frame's road-plane removal (utils/refinement.py:628-644).

@@ -9,7 +9,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDFR_LIB") or os.path.join(_HERE, "lib", "libsdfr_hip.so")     # SDFR_LIB: A/B builds (tools/ab_build.sh)
 
-ABI_VERSION = 408          # include/sdfr.h SDFR_VERSION
+ABI_VERSION = 409          # include/sdfr.h SDFR_VERSION
 _lib = None
 
 # name -> (restype, argtypes); mirrors include/sdfr.h one to one
@@ -192,6 +192,8 @@ _PROTOS = {
     "sdfr_css_input": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
     "sdfr_depth_map_masked": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # augmentation of the CSS training crops (csrc/augment.hip)
+    "sdfr_augment": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 9),
     # lidar normals for the road-plane removal (csrc/normals.hip)
     "sdfr_lidar_normals_ws_bytes": (c_int64, [c_int]),
     "sdfr_lidar_normals": (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,

@@ -46,9 +46,10 @@ $HIPCC $COMMON -ffp-contract=off -c "$HERE/box_iou.hip" -o "$HERE/obj/box_iou.o"
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/detection_eval.hip" -o "$HERE/obj/detection_eval.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/frame.hip" -o "$HERE/obj/frame.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/ingest.hip" -o "$HERE/obj/ingest.o" &
+$HIPCC $COMMON -ffp-contract=off -c "$HERE/augment.hip" -o "$HERE/obj/augment.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/normals.hip" -o "$HERE/obj/normals.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/css_head.hip" -o "$HERE/obj/css_head.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/css_train.hip" -o "$HERE/obj/css_train.o" &
 wait
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/${SDFR_LIBNAME:-libsdfr_hip.so}" "$HERE"/obj/{common,mlp,mlp_fwd32,mlp_fwd16,mlp_split,mlp_jac,mlp_jac16,mlp_persist,mlp_small,mlp_ln,surface,project,splat,params,losses,trace,pose,box_iou,detection_eval,frame,ingest,normals,css_head,css_train}.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/${SDFR_LIBNAME:-libsdfr_hip.so}" "$HERE"/obj/{common,mlp,mlp_fwd32,mlp_fwd16,mlp_split,mlp_jac,mlp_jac16,mlp_persist,mlp_small,mlp_ln,surface,project,splat,params,losses,trace,pose,box_iou,detection_eval,frame,ingest,augment,normals,css_head,css_train}.o
 echo "built $OUT/${SDFR_LIBNAME:-libsdfr_hip.so}"

@@ -141,51 +141,15 @@ extern "C" int sdfr_match_boxes(const double* anno, int A, const double* det, in
 }
 
 // ---- CSS input ---------------------------------------------------------------------------------------------------------------------------
-#define CSS_OUT 128                  // transforms.Resize((128, 128))
+#include "css_resample.h"             // CSS_OUT, CSS_PRECISION_BITS, css_coef_row, css_clip8: shared with augment.hip
 #define CSS_META 8                   // int32 per annotation: l, t, crop width, crop height, first mask element (-1: none), first row of the
                                      // annotation in tmp, first workgroup of the annotation in the horizontal pass, unused
-#define CSS_PRECISION_BITS 22        // Pillow's 32 - 8 - 2
 
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc for the triangle filter (support 1), in double like its C.  One thread per output index
-// of one pass (pass 0: horizontal, crop width -> 128; pass 1: vertical, crop height -> 128) of one annotation.
+// One thread per output index of one pass (pass 0: horizontal, crop width -> 128; pass 1: vertical, crop height -> 128) of one annotation.
 // coef[a][pass][xx] = { xmin, n, kk[0 .. ksize) }.
 __global__ __launch_bounds__(CSS_OUT) void sdfr_css_coef_kernel(const int32_t* __restrict__ meta, int ksize, int32_t* __restrict__ coef) {
     const int a = blockIdx.x >> 1, pass = blockIdx.x & 1, xx = threadIdx.x;
-    const int inS = meta[CSS_META * a + 2 + pass];
-    int32_t* out = coef + ((int64_t)blockIdx.x * CSS_OUT + xx) * (2 + ksize);
-    const double scale = (double)inS / (double)CSS_OUT;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * fs;
-    const double center = 0.0 + (xx + 0.5) * scale;
-    const double ss = 1.0 / fs;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > inS) xmax = inS;
-    int n = xmax - xmin;
-    if (n > ksize) n = ksize;                                           // cannot happen for ksize = ceil(support) * 2 + 1; guards the table
-    if (n < 0) n = 0;
-    double ww = 0.0;
-    for (int x = 0; x < n; ++x) {
-        double t = (x + xmin - center + 0.5) * ss;
-        if (t < 0.0) t = -t;
-        const double wgt = t < 1.0 ? 1.0 - t : 0.0;
-        ww += wgt;
-    }
-    out[0] = xmin;
-    out[1] = n;
-    for (int x = 0; x < n; ++x) {
-        double t = (x + xmin - center + 0.5) * ss;                      // the same operations as above: the same bits
-        if (t < 0.0) t = -t;
-        double wgt = t < 1.0 ? 1.0 - t : 0.0;
-        if (ww != 0.0) wgt /= ww;
-        out[2 + x] = (int)(0.5 + wgt * (double)(1 << CSS_PRECISION_BITS));      // no negative taps in the triangle filter
-    }
-}
-
-__device__ __forceinline__ uint32_t css_clip8(int v) {
-    v >>= CSS_PRECISION_BITS;
-    return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+    css_coef_row(meta[CSS_META * a + 2 + pass], xx, ksize, coef + ((int64_t)blockIdx.x * CSS_OUT + xx) * (2 + ksize));
 }
 
 // Horizontal pass: thread = (row of the crop, four neighbouring output columns), 8 rows per workgroup; a flat list of workgroups over the

@@ -3,8 +3,10 @@
 autograd as before; no [B][256][H][W] tensor exists at any point of a step.
 
 train_step(net, optimizer, batch)    one optimisation step on a batch of the reference's Crops dataset
-train_css(cfgp, trainloader=None)    the reference's loop: Adam, `lr` and `epochs` from the config, its print line, css.pt (the reference's
-                                     state_dict names) under <log dir>/net every `analyse_epoch` epochs
+train_css(cfgp, trainloader=None, augment=None)
+                                     the reference's loop: Adam, `lr` and `epochs` from the config, its print line, css.pt (the reference's
+                                     state_dict names) under <log dir>/net every `analyse_epoch` epochs; augment='device' reads the crops with
+                                     sdflabel_amd.datasets.crops and augments them on the device (no torchvision)
 
 The image dumps of the reference (torchvision.utils.save_image) are not written."""
 import os
@@ -37,13 +39,21 @@ def train_step(net, optimizer, batch, device=None):
     return {k: v.detach() for k, v in losses.items()}
 
 
-def train_css(cfgp, trainloader=None):
+def train_css(cfgp, trainloader=None, augment=None):
     """Training of the CSS network (the reference's train_css).  cfgp: a ConfigParser with the reference's keys ([input] css_path, data_path;
     [train] lr, batch_size, epochs; [log] dir, analyse_epoch; [optimization] cpu_threads).
 
     trainloader: any iterable of the reference's batches with a .dataset.  With trainloader=None the loader is built as the reference builds
     it, from the CALLER's datasets.crops.Crops: that module is the reference's own and is not ported here (its augmentations need
-    torchvision, which this package does not depend on), so it has to be importable from the caller's path."""
+    torchvision, which this package does not depend on), so it has to be importable from the caller's path.
+
+    augment: None keeps that behaviour.  'device' (with trainloader=None) builds sdflabel_amd.datasets.crops.DeviceCropLoader over
+    sdflabel_amd.datasets.crops.Crops from the config's data_path and batch_size: the reference's augmentation, byte for byte Pillow's for
+    the same random parameters, batched on the device (sdflabel_amd.augment)."""
+    if augment not in (None, 'device'):
+        raise ValueError("train_css: augment must be None or 'device', got %r" % (augment,))
+    if augment is not None and trainloader is not None:
+        raise ValueError("train_css: augment=%r builds the loader itself; pass either it or trainloader" % (augment,))
     if not torch.cuda.is_available():
         from .._lib import SdfrError
         raise SdfrError("train_css: sdflabel_amd runs on the GPU only; there is no CPU fallback")
@@ -54,12 +64,20 @@ def train_css(cfgp, trainloader=None):
     optimizer = torch.optim.Adam(css_net.parameters(), lr=lr)
     log_dir = _cfg(cfgp, 'log', 'dir', 'log', str)
     os.makedirs(log_dir, exist_ok=True)
-    if trainloader is None:
+    if augment == 'device':
+        from ..datasets.crops import Crops, DeviceCropLoader
+        trainloader = DeviceCropLoader(Crops(_cfg(cfgp, 'input', 'data_path', None, str)), _cfg(cfgp, 'train', 'batch_size', 32, int),
+                                       shuffle=True, device=device)
+    elif trainloader is None:
         from datasets.crops import Crops                   # the caller's (the reference's) dataset
         batch_size = _cfg(cfgp, 'train', 'batch_size', 32, int)
         cpu_threads = _cfg(cfgp, 'optimization', 'cpu_threads', 3, int)
         data_path = _cfg(cfgp, 'input', 'data_path', None, str)
-        trainloader = torch.utils.data.DataLoader(Crops(data_path), batch_size=batch_size, shuffle=True, num_workers=cpu_threads)
+        if Crops.__module__ == 'sdflabel_amd.datasets.crops':  # the compat path resolved it to this package's dataset (raw uint8 images):
+            from ..datasets.crops import DeviceCropLoader      # that one is batched by the device loader, not by DataLoader's collate
+            trainloader = DeviceCropLoader(Crops(data_path), batch_size, shuffle=True, device=device)
+        else:
+            trainloader = torch.utils.data.DataLoader(Crops(data_path), batch_size=batch_size, shuffle=True, num_workers=cpu_threads)
     epochs = _cfg(cfgp, 'train', 'epochs', 1000, int)
     analyse_epoch = _cfg(cfgp, 'log', 'analyse_epoch', 10, int)
     for epoch in range(epochs):
