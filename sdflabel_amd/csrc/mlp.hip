@@ -90,7 +90,7 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
             }
         for (int r = 0; r < L.out_dim; ++r) bias[(size_t)l * HP + r] = h_b[l][r];
     }
-    // k-major image of the exact-f32 grid forward's compacted products (mlp_kernel.h, KC): Wk[k][row] at float offset 4 off_f of the
+    // k-major image of the exact-f32 grid forward's compacted products (mlp_kernel.h, KC): Wk[k][sdfr_wk_row(row)] at float offset 4 off_f of the
     // layer, zero padded like Wf.  Skipping a zero activation is exact only while 0 * w == 0, i.e. for finite weights: a decoder with an
     // inf or NaN weight keeps the full K chain.
     std::vector<float> Wk;
@@ -103,7 +103,7 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
                 for (int k = 0; k < L.in_dim; ++k) {
                     const float w = h_W[l][(size_t)r * L.in_dim + k];
                     finite = finite && std::isfinite(w);
-                    Wk[(size_t)L.off_f * 4 + (size_t)k * HP + r] = w;
+                    Wk[(size_t)L.off_f * 4 + (size_t)k * HP + sdfr_wk_row(r)] = w;
                 }
         }
     }

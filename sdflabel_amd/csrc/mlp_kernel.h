@@ -189,6 +189,9 @@ __device__ __forceinline__ void store4(h16* dst, const float* v) {
 __device__ __forceinline__ int64_t sdfr_mask_dword(int64_t r, int l, int n_layers, int HP32, int j) {
     return (((r >> 7) * n_layers + l) * 128 + (r & 127)) * HP32 + (j >> 5);
 }
+// Row order of the k-major image Wk (per-tile K compaction of the exact-f32 grid forward, KC below): inside a wave's block of 64 rows the
+// two rows a lane feeds to its two feature tiles, r and r + 32, are neighbours.
+__host__ __device__ __forceinline__ int sdfr_wk_row(int r) { return (r & ~63) | ((r & 31) << 1) | ((r >> 5) & 1); }
 __device__ __forceinline__ int sdfr_mask_shift(int j) { return ((j >> 2) & 1) * 16 + ((j & 31) >> 3) * 4 + (j & 3); }
 
 // ET   operand element type (float: exact f32; _Float16: half operands, f32 accumulate -- forward modes and the mask-fed Jacobian)
@@ -209,8 +212,14 @@ __device__ __forceinline__ int sdfr_mask_shift(int j) { return ((j >> 2) & 1) * 
 //      2 PERSIST  the launch is a fixed pool of workgroups that walk the LIVE tiles of a ragged [B][crop_rows] launch (per-crop counts) or of a
 //                 skip launch (per-crop flags): dead tiles cost nothing, a launch with nothing to do costs one wave of dispatch, and the last
 //                 round of a many-crop launch is as full as the live tile count allows
+// KC2: the exact-f32 grid forward on 32-row tiles (NP = 1), 8 waves.  Its operand tile is 64 KiB, so TWO workgroups are resident per CU
+// (four waves per SIMD: the register allocation is bounded to 128 per wave) and one tile's K loop runs under the other's epilogue and
+// barriers.
+template <typename ET, int MS, int FT, int NP, int NW, int MODE, bool LN, int XF> constexpr bool sdfr_mlp_kc2() {
+    return sizeof(ET) == 4 && MS == 32 && FT == 2 && NP == 1 && NW == 8 && (MODE == 0 || MODE == 1) && !LN && XF == 0;
+}
 template <typename ET, int MS, int FT, int NP, int NW, int PF, int MODE, int PFB_ = 0, bool LN = false, int XF = 0>
-__global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const MlpParams P) {
+__global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN, XF>() ? 4 : SDFR_MLP_WPE)) void sdfr_mlp_kernel(const MlpParams P) {
     typedef Mma<ET, MS> M;
     typedef typename M::acc_t acc_t;
     typedef typename M::vec_t vec_t;
@@ -284,9 +293,12 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
     // non-zero at some point of the tile and writes them to consecutive operand slots, in the order in which the full K chain visits them;
     // the next product walks that shorter list and gathers its weights from the k-major image Wk.  A skipped term is fma(0, w, acc) == acc
     // (up to the sign of a zero accumulator, which no ReLU output keeps), so every output and mask bit is the full chain's.
-    constexpr bool KC = !HALF && MS == 32 && FT == 2 && NP == 2 && NW == 8 && (MODE == 0 || MODE == 1) && !LN && XF == 0;
+    constexpr bool KC2 = sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN, XF>();
+    constexpr bool KC = !HALF && MS == 32 && FT == 2 && (NP == 2 || NP == 1) && NW == 8 && (MODE == 0 || MODE == 1) && !LN && XF == 0;
     __shared__ int4 kc_list4[KC ? HP / 4 : 1];                    // operand slot -> k * HP (element offset of the k-row in Wk)
     __shared__ int kc_cnt[KC ? NW : 1];                           // surviving features per wave (published by the layer's first barrier)
+    static_assert(!KC2 || (KC && sizeof(lds4) + sizeof(jinj) + sizeof(jpfx) + sizeof(kc_list4) + sizeof(kc_cnt) <= 80 * 1024),
+                  "KC2: two workgroups per CU, at most 80 KiB of LDS each");
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -752,27 +764,29 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
         }
     };
     // KC product: the operand holds nk compacted slots (a multiple of 2 KT), slot s = k-tile s / KT, lane group (s % KT) / KV, component
-    // s % KV -- the place where the full chain would have visited its feature.  A lane's weight fragment is gathered as KV dwords of the
-    // k-major image (Wk[k][row]: 32 lanes of a lane group read 128 contiguous bytes per load); the k list is read from LDS one tile ahead of
+    // s % KV -- the place where the full chain would have visited its feature.  A lane's weight fragments of BOTH feature tiles are gathered
+    // as KV 8-byte pairs of the k-major image (Wk[k][sdfr_wk_row(row)]: 32 lanes of a lane group read 256 contiguous bytes per load; with one
+    // 4-byte gather per feature tile the loop ran 13 % short of its matrix rate); the k list is read from LDS one tile ahead of
     // the gather it feeds.  Ring of two tiles and clamped prefetch indices, as in gemm_body's branch-free loop.
     auto gemm_kc_body = [&](const float* __restrict__ Wl, int nk, int nact, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
         const int nkt = nk / KT;
         if (nkt <= 0) return;
-        const float* wp = Wl + fbase + lp;
+        const float* wp = Wl + fbase + 2 * lp;
         const vec_t* bptr = act + lg * PT + lp;
         const int4* klp = kc_list4 + lg;
         vec_t a[2][FT], b[2][NP];
         int4 ko[2];
+        // (KC kernels have FT = 2; Wk keeps a lane's two rows of one k side by side -- sdfr_wk_row --: ONE 8-byte gather per k and lane instead of one per feature tile)
         auto load_a = [&](const int4& k, vec_t* aa) {
+            const float2 w0 = *reinterpret_cast<const float2*>(wp + k.x), w1 = *reinterpret_cast<const float2*>(wp + k.y);
+            const float2 w2 = *reinterpret_cast<const float2*>(wp + k.z), w3 = *reinterpret_cast<const float2*>(wp + k.w);
+            aa[0][0] = w0.x; aa[0][1] = w1.x; aa[0][2] = w2.x; aa[0][3] = w3.x;
+            if (FULL || nact > 1) { aa[FT - 1][0] = w0.y; aa[FT - 1][1] = w1.y; aa[FT - 1][2] = w2.y; aa[FT - 1][3] = w3.y; }
+            else {
 #pragma unroll
-            for (int f = 0; f < FT; ++f)
-                if (FULL || f < nact) {
-                    aa[f][0] = wp[k.x + f * MS]; aa[f][1] = wp[k.y + f * MS]; aa[f][2] = wp[k.z + f * MS]; aa[f][3] = wp[k.w + f * MS];
-                } else {
-#pragma unroll
-                    for (int i = 0; i < KV; ++i) aa[f][i] = (ET)0;
-                }
+                for (int i = 0; i < KV; ++i) aa[FT - 1][i] = (ET)0;
+            }
         };
         auto load_b = [&](int tile, vec_t* bb) {
             const vec_t* bp = bptr + tile * (NLG * PT);
@@ -1028,7 +1042,7 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
             if (wave == NW - 1) {
                 for (int e = 0; e < padded - tot; ++e) {
                     const int s = slot_of(tot + e);
-                    act_e[((s / KV) * PT + lane) * KV + (s % KV)] = 0.f;          // (PT == 64: lane = point)
+                    if (lane < PT) act_e[((s / KV) * PT + lane) * KV + (s % KV)] = 0.f;       // (lane = point)
                     if (lane == e) reinterpret_cast<int*>(kc_list4)[s] = 0;
                 }
             }
@@ -1178,8 +1192,10 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
         // k slices of the last linear's dot product.  Half operands: ONE partition (4 slices of 128 k, summed in order) for every tile
         // geometry, so that a row's value has the same bits whether a 128-, 64- or 16-row tile evaluated it (r04: the sphere tracer's
         // march picks the tile size by the device-side row count, and a crop must march the same alone and in a batch); float32: as many
-        // slices as the workgroup has threads per point (unchanged bits).
-        constexpr int SL = HALF ? (NT / PT < 4 ? NT / PT : 4) : NT / PT;       // (fewer than 4 threads per point: A/B geometries only)
+        // slices as the workgroup has threads per point (unchanged bits) -- except KC2: the grid forward's partition stays the 64-row tile's,
+        // 8 slices of 64 k summed in order, so that a row has the same bits under both tile sizes; the threads beyond 8 PT idle here.
+        constexpr int SL = HALF ? (NT / PT < 4 ? NT / PT : 4) : (KC2 ? 8 : NT / PT);       // (fewer than 4 threads per point: A/B geometries only)
+        static_assert(!KC || (SL == 8 && KG / SL * KV == 64), "exact-f32 grid forward: last linear in 8 slices of 64 k, whatever the tile");
         static_assert(SL * PT <= NT, "last linear: one thread per (slice, point)");
         constexpr int KGS = KG / SL;
         const int sl = tid / PT, pt = tid - sl * PT;

@@ -22,7 +22,8 @@ def _cfg(cfgp, section, key, default, conv):
 
 def train_step(net, optimizer, batch, device=None):
     """One step: batch is a dict with 'rgb' [B][3][H][W] float, 'mask' [B][H][W], 'uvw' [B][3][H][W] (integer classes 0 ... 255) and 'latent'
-    [B][3] (or [1][B][3], which the reference squeezes).  Returns the four loss values as detached tensors {'loss', 'uvw', 'mask', 'latent'}."""
+    [B][3] (or [1][B][3], which the reference squeezes).  Returns the four loss values as detached tensors {'loss', 'uvw', 'mask', 'latent'}.
+    Reproducible: the same weights and batch give the same bits in every call."""
     device = device if device is not None else next(net.parameters()).device
     rgb = batch['rgb'].to(device).float()
     mask_gt = batch['mask'].to(device)
@@ -33,8 +34,16 @@ def train_step(net, optimizer, batch, device=None):
     if uvw_gt.dtype != torch.uint8:
         uvw_gt = uvw_gt.long()
     optimizer.zero_grad()
-    losses = net.loss(rgb, uvw_gt, mask_gt, latent_gt)
-    losses['loss'].backward()
+    # The body's convolutions run with the library's deterministic solvers: with the default choice layer2's output, and with it every loss
+    # and gradient, changed in the last bits from call to call for the same weights and images (the fused head losses have no atomics and
+    # never did).  A step then has the same bits whenever it is repeated.  The caller's setting is restored on the way out.
+    was = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    try:
+        losses = net.loss(rgb, uvw_gt, mask_gt, latent_gt)
+        losses['loss'].backward()
+    finally:
+        torch.backends.cudnn.deterministic = was
     optimizer.step()
     return {k: v.detach() for k, v in losses.items()}
 
