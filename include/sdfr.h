@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 409        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 410        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -42,7 +42,8 @@ extern "C" {
  * sdfr_image_box_iou; 403: the evaluator's statistics sdfr_eval_*; 404: frame labelling, sdfr_reproject and
  * sdfr_point_extents; 405: frame ingest, sdfr_depth_map, sdfr_match_boxes and sdfr_css_input; 406: the CSS output head, sdfr_css_head and
  * sdfr_css_latent; 407: its training losses and gradients, sdfr_css_head_loss and sdfr_css_latent_loss; 408: the road-plane removal, sdfr_lidar_normals_ws_bytes,
- * sdfr_lidar_normals and sdfr_depth_map_masked; 409: the training-crop augmentation, sdfr_augment).  A caller built
+ * sdfr_lidar_normals and sdfr_depth_map_masked; 409: the training-crop augmentation, sdfr_augment; 410: the grid forward with the caller's tile order,
+ * sdfr_grid_tile_order and sdfr_mlp_forward_ordered).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -87,6 +88,18 @@ int sdfr_mlp_forward(const sdfr_decoder* dec, const float* inputs, int64_t n, fl
                      uint32_t* mask_ws /* optional: sdfr_decoder_mask_words(dec, n) uint32 words; receives the ReLU masks
                                           (1 bit per hidden feature, point and layer) for a later sdfr_mlp_jacobian */,
                      void* stream);
+/* Tile order of the exact-f32 grid forward for a D^3 grid (row = x D D + y D + z), computed on the host: out[D^3] receives the rows block by
+ * block -- 4x4x4 blocks in lexicographic (bx, by, bz) order, a block's rows in (x, y, z) order, blocks at the border clipped.  A permutation
+ * of 0 .. D^3 - 1; for D divisible by 4 every run of 64 entries is one block.  1 <= D <= 1024. */
+int sdfr_grid_tile_order(int D, int32_t* out);
+/* sdfr_mlp_forward with the rows that share a tile chosen by the caller: slot j of the launch evaluates row
+ * (j / order_rows) * order_rows + order[j % order_rows] and stores value and masks AT THAT ROW, so sdf and mask_ws receive what
+ * sdfr_mlp_forward writes, bit for bit.  What changes is what the per-tile K compaction can leave out (spatially compact tiles keep fewer
+ * hidden features alive).  order: DEVICE int32 [order_rows], a permutation of 0 .. order_rows - 1 (an entry outside that range makes its
+ * slot evaluate nothing: the row it should have named is left unwritten); n must be a multiple of order_rows (n / order_rows crops of
+ * order_rows rows each; order_rows need not be a multiple of the tile).  Float32 decoders of padded width 512 without LayerNorm. */
+int sdfr_mlp_forward_ordered(const sdfr_decoder* dec, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, const int32_t* order,
+                             int64_t order_rows, void* stream);
 /* the same with float16 operands on the matrix cores (weights and hidden activations rounded to half, float32 accumulation, bias,
  * ReLU and tanh) -- the decoder precision of the reference's default config (configs/config_refine.ini:19); inputs/outputs stay float32. */
 int sdfr_mlp_forward_f16(const sdfr_decoder* dec, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, void* stream);

@@ -25,6 +25,7 @@ Independent of the mode: binned (from 4 crops per launch the splat uses per-tile
 refinement: decoder, band and Jacobian once per latent) and fused / fused_head / fused_tail (False: the longer launch sequences, same bits).
 """
 import math
+import os
 
 import torch
 
@@ -65,6 +66,15 @@ class BatchRenderer:
         self.L, self.NI = decoder.latent_size, decoder.latent_size + 3
         self.grid = Grid3D(density, dev).points.detach().contiguous()
         self.G = self.grid.shape[0]
+        # Tile order of the exact-f32 full-grid forward (include/sdfr.h: sdfr_grid_tile_order): a tile is a 4x4x4 block of the grid, not 64
+        # consecutive rows, so that the per-tile K compaction finds more to skip.  The grid is a constant of the renderer: the
+        # order is built on the host and uploaded once, a launch allocates nothing.  Same bits either way; SDFR_FWD_ORDER=0 in the environment,
+        # read at every launch, selects the plain launch (A/B timing and the parity tests).
+        self.fwd_order = None
+        if prec == torch.float32 and self.handle.hp == 512 and not self.handle.has_ln and self.G == int(density) ** 3:
+            order = torch.empty(self.G, dtype=torch.int32)
+            ck(_lib.lib().sdfr_grid_tile_order(int(density), P(order)), "sdfr_grid_tile_order")
+            self.fwd_order = order.to(dev)
         self.cap = int(cap) if cap is not None else max(256, self.G // 8)       # surfel capacity per crop
         self._init_extents(K, max_pixels, max_side)
         self._alloc_common()
@@ -404,7 +414,11 @@ class BatchRenderer:
         """the mode's kernel over the whole grid (values + ReLU masks) -> band -> mask-fed Jacobian of the band rows"""
         B, G, cap = self.B, self.G, self.cap
         fwd = L.sdfr_mlp_forward_f16 if self.f16 else (L.sdfr_mlp_forward_split if self.split else L.sdfr_mlp_forward)
-        ck(fwd(self.handle.h, P(self.inputs), B * G, P(self.sdf), P(self.mask_ws), st), fwd.__name__)
+        if self.fwd_order is not None and os.environ.get("SDFR_FWD_ORDER", "1") != "0":
+            ck(L.sdfr_mlp_forward_ordered(self.handle.h, P(self.inputs), B * G, P(self.sdf), P(self.mask_ws), P(self.fwd_order), G, st),
+               "sdfr_mlp_forward_ordered")
+        else:
+            ck(fwd(self.handle.h, P(self.inputs), B * G, P(self.sdf), P(self.mask_ws), st), fwd.__name__)
         if mlp_events is not None:
             mlp_events[1].record()
         ck(L.sdfr_band_select_ex(P(self.sdf), G, B, self.thr, None, None, P(self.idx), cap, P(self.cnt), None, P(self.scratch), P(self.over), 1, st),

@@ -191,6 +191,47 @@ extern "C" int sdfr_mlp_forward(const sdfr_decoder* d, const float* inputs, int6
     return SDFR_OK;
 }
 
+// Tile order of the exact-f32 grid forward over a D^3 grid (row = x D D + y D + z): the index space cut into 4x4x4 blocks, blocks in
+// lexicographic (bx, by, bz) order, the rows of a block in (x, y, z) order, blocks at the border clipped.  For D divisible by 4 every run of
+// 64 entries is one block (a 64-row tile), every run of 32 a 2x4x4 half of one (a 32-row tile): the decoder's ReLU pattern is spatially
+// coherent, so a compact block keeps fewer features alive than 64 consecutive rows, a 1 x 2 x 40 sliver at D = 40.  Host only.
+extern "C" int sdfr_grid_tile_order(int D, int32_t* out) {
+    SDFR_REQUIRE(out, "sdfr_grid_tile_order: NULL argument");
+    SDFR_REQUIRE(D >= 1 && D <= 1024, "sdfr_grid_tile_order: D=%d outside [1,1024]", D);
+    int64_t j = 0;
+    for (int bx = 0; bx < D; bx += 4)
+        for (int by = 0; by < D; by += 4)
+            for (int bz = 0; bz < D; bz += 4)
+                for (int x = bx; x < bx + 4 && x < D; ++x)
+                    for (int y = by; y < by + 4 && y < D; ++y)
+                        for (int z = bz; z < bz + 4 && z < D; ++z) out[j++] = (int32_t)(((int64_t)x * D + y) * D + z);
+    return SDFR_OK;
+}
+
+// sdfr_mlp_forward with the rows of a tile chosen by the caller: slot j of the launch evaluates row (j / order_rows) order_rows + order[j %
+// order_rows] and stores its value and masks at that row, so the outputs are those of sdfr_mlp_forward bit for bit (a row's arithmetic does
+// not depend on its tile's other rows; mlp_kernel.h, KC) -- what changes is what the per-tile K compaction can skip.  A slot whose index is
+// outside [0, order_rows) evaluates nothing: the row it should have named keeps what the buffers held.
+extern "C" int sdfr_mlp_forward_ordered(const sdfr_decoder* d, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, const int32_t* order,
+                                        int64_t order_rows, void* stream) {
+    SDFR_REQUIRE(d && inputs && sdf && order, "sdfr_mlp_forward_ordered: NULL argument");
+    SDFR_REQUIRE(n >= 0 && n < (int64_t)1 << 31, "sdfr_mlp_forward_ordered: n=%lld out of range", (long long)n);
+    SDFR_REQUIRE(order_rows > 0, "sdfr_mlp_forward_ordered: order_rows=%lld must be positive", (long long)order_rows);
+    SDFR_REQUIRE(n % order_rows == 0, "sdfr_mlp_forward_ordered: n=%lld is not a multiple of order_rows=%lld", (long long)n, (long long)order_rows);
+    SDFR_REQUIRE(d->HP == 512 && !d->has_ln, "sdfr_mlp_forward_ordered: needs a float32 decoder of padded width 512 without LayerNorm (this one: %d%s)",
+                 d->HP, d->has_ln ? ", LayerNorm" : "");
+    // (the kernel keeps a row's 64-byte mask line of layer 0 as an int32)
+    SDFR_REQUIRE(!mask_ws || ((n + 127) / 128) * 128 * (int64_t)(d->n_lin - 1) < (int64_t)1 << 31,
+                 "sdfr_mlp_forward_ordered: n=%lld rows with masks of %d layers exceed the kernel's line index", (long long)n, d->n_lin - 1);
+    SDFR_DEVICE_CHECK(d, "sdfr_mlp_forward_ordered");
+    if (n == 0) return SDFR_OK;
+    MlpParams P = d->proto;
+    P.inputs = inputs; P.n = n; P.sdf = sdf; P.maskbuf = mask_ws; P.trace = g_trace;
+    sdfr_launch_fwd_f32_512_ordered(P, n, order, order_rows, (hipStream_t)stream);
+    SDFR_LAUNCH_CHECK();
+    return SDFR_OK;
+}
+
 #ifndef SDFR_COUNTED_TILE16_ROWS
 #define SDFR_COUNTED_TILE16_ROWS 4096      // 256 CUs x 16 rows: below this every 16-row tile has a CU of its own
 #endif

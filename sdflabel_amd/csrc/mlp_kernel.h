@@ -80,6 +80,7 @@ struct MlpParams {
     int64_t crop_rows;           // start at or beyond their crop's count exit (candidate rows of the float16 reuse mode, r05)
     const int32_t* gather_idx;   // GATHER kernels (r06): row s of crop c of the ragged [B][crop_rows] launch is inputs[c * gather_rows + gather_idx[c * crop_rows + s]]
     int64_t gather_rows;         // (s < crop_cnt[c]; rows beyond the count read the crop's row 0) -- the candidate rows are read where they lie, no copy
+                                 // ORDER kernels: gather_idx = the tile order (gather_rows int32: a permutation of the rows of one crop), gather_rows = G
     int n_crops;                 // PERSIST kernels (r06): crops of the ragged / skip launch (the workgroups walk the LIVE tiles only)
     const int32_t* n_dev;        // forward: optional device-side row count (rows >= *n_dev are not evaluated; n is the launch bound)
     int n_dev_lo, n_dev_hi;      // with n_dev and n_dev_hi > 0: the launch runs only while n_dev_lo <= *n_dev < n_dev_hi (two tile geometries of one step)
@@ -212,11 +213,14 @@ __device__ __forceinline__ int sdfr_mask_shift(int j) { return ((j >> 2) & 1) * 
 //      2 PERSIST  the launch is a fixed pool of workgroups that walk the LIVE tiles of a ragged [B][crop_rows] launch (per-crop counts) or of a
 //                 skip launch (per-crop flags): dead tiles cost nothing, a launch with nothing to do costs one wave of dispatch, and the last
 //                 round of a many-crop launch is as full as the live tile count allows
+//      4 ORDER    (mlp_fwd32.hip) slot j of the launch evaluates row (j / G) G + order[j % G] (P.gather_idx = order, P.gather_rows = G rows per
+//                 crop): which rows share a tile is the caller's choice -- 4x4x4 blocks of the grid keep fewer features alive per tile than 64
+//                 consecutive rows (KC below).  Values and masks are stored at the ROW, so every consumer reads them as before
 // KC2: the exact-f32 grid forward on 32-row tiles (NP = 1), 8 waves.  Its operand tile is 64 KiB, so TWO workgroups are resident per CU
 // (four waves per SIMD: the register allocation is bounded to 128 per wave) and one tile's K loop runs under the other's epilogue and
 // barriers.
 template <typename ET, int MS, int FT, int NP, int NW, int MODE, bool LN, int XF> constexpr bool sdfr_mlp_kc2() {
-    return sizeof(ET) == 4 && MS == 32 && FT == 2 && NP == 1 && NW == 8 && (MODE == 0 || MODE == 1) && !LN && XF == 0;
+    return sizeof(ET) == 4 && MS == 32 && FT == 2 && NP == 1 && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0;
 }
 template <typename ET, int MS, int FT, int NP, int NW, int PF, int MODE, int PFB_ = 0, bool LN = false, int XF = 0>
 __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN, XF>() ? 4 : SDFR_MLP_WPE)) void sdfr_mlp_kernel(const MlpParams P) {
@@ -231,6 +235,8 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     constexpr bool GMASK = MODE == 3;
     constexpr bool GATHER = (XF & 1) != 0;
     constexpr bool PERSIST = (XF & 2) != 0;
+    constexpr bool ORDER = (XF & 4) != 0;
+    static_assert(!ORDER || (XF == 4 && (MODE == 0 || MODE == 1) && sizeof(ET) == 4 && MS == 32 && FT == 2), "ORDER: the exact-f32 grid forward alone");
     static_assert(XF == 0 || (MODE == 0 || MODE == 1) || (MODE == 3 && XF == 2), "GATHER is a forward feature; PERSIST: forward modes and the mask-fed Jacobian");
     constexpr bool JPOOL = JAC && PERSIST;                         // the mask-fed Jacobian as a pool over the crops' live band tiles (r06)
     static_assert(!SAVE || MS == 32, "mask layout assumes 32x32 forward tiles");
@@ -294,7 +300,7 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     // the next product walks that shorter list and gathers its weights from the k-major image Wk.  A skipped term is fma(0, w, acc) == acc
     // (up to the sign of a zero accumulator, which no ReLU output keeps), so every output and mask bit is the full chain's.
     constexpr bool KC2 = sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN, XF>();
-    constexpr bool KC = !HALF && MS == 32 && FT == 2 && (NP == 2 || NP == 1) && NW == 8 && (MODE == 0 || MODE == 1) && !LN && XF == 0;
+    constexpr bool KC = !HALF && MS == 32 && FT == 2 && (NP == 2 || NP == 1) && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0;
     __shared__ int4 kc_list4[KC ? HP / 4 : 1];                    // operand slot -> k * HP (element offset of the k-row in Wk)
     __shared__ int kc_cnt[KC ? NW : 1];                           // surviving features per wave (published by the layer's first barrier)
     static_assert(!KC2 || (KC && sizeof(lds4) + sizeof(jinj) + sizeof(jpfx) + sizeof(kc_list4) + sizeof(kc_cnt) <= 80 * 1024),
@@ -436,6 +442,20 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                 const int64_t c = r0 / P.crop_rows, sc = r0 - c * P.crop_rows + tid;
                 const bool live = sc < (int64_t)P.crop_cnt[c];          // beyond the count: the crop's row 0 (finite padding rows of the last tile)
                 rows[tid] = (int)(c * P.gather_rows + (live ? P.gather_idx[c * P.crop_rows + sc] : 0));
+            }
+        } else
+        if constexpr (ORDER) {
+            // slots[] (forward modes do not use it otherwise): the row a slot's value and masks go to, -1 for none -- slots beyond the launch's
+            // rows, and slots whose index lies outside [0, G): those read the first row of the tile's first crop (finite) and store nothing.
+            // olines[] (gy's place): the row's 64-byte line of layer 0 in the mask workspace (layout v2), worked out here once per tile.
+            if (tid < PT) {
+                const int64_t G = P.gather_rows, j = r0 + tid, c = j / G;
+                const int o = tid < n_valid ? P.gather_idx[j - c * G] : -1;
+                const bool ok = o >= 0 && (int64_t)o < G;
+                const int64_t row = ok ? c * G + o : (r0 / G) * G;
+                rows[tid] = (int)row;
+                slots[tid] = ok ? (int)row : -1;
+                reinterpret_cast<int*>(gy)[tid] = ok ? (int)((row >> 7) * P.n_mfma * 128 + (row & 127)) : -1;
             }
         } else
         if (tid < PT) rows[tid] = TAIL ? (int)((int64_t)blockIdx.x * PT + tid) : (int)(r0 + (tid < n_valid ? tid : 0));
@@ -1159,6 +1179,13 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                     const uint32_t mine = h0 | (h1 << 16);
                     const uint32_t other = (uint32_t)__shfl_xor((int)mine, 32, 64);
                     const uint32_t lo = lg == 0 ? mine : other, hi = lg == 0 ? other : mine;         // lane group 0's / 1's halves
+                    if constexpr (ORDER) {
+                        // the slot's own row (olines[], filled with rows[]): a 4x4x4 block's rows lie in up to 16 runs of 4 rows
+                        const int oline = reinterpret_cast<const int*>(gy)[p * MS + lp];
+                        if (lg == (p & 1) && oline >= 0)
+                            reinterpret_cast<uint2*>(P.maskbuf)[((int64_t)oline + l * 128) * (HP / 64) + (fbase >> 6)] =
+                                make_uint2((lo & 0xffffu) | (hi << 16), (lo >> 16) | (hi & 0xffff0000u));
+                    } else
                     if (lg == (p & 1))
                         mb2[((int)(row0 & 127) + p * MS + lp) * (HP / 64) + (fbase >> 6)] = make_uint2((lo & 0xffffu) | (hi << 16), (lo >> 16) | (hi & 0xffff0000u));
                 }
@@ -1273,6 +1300,9 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                     }
                   }
                 }
+            } else if constexpr (ORDER) {
+                const int row = slots[tid];
+                if (row >= 0 && (!P.skip || !P.skip[row / P.skip_rows])) P.sdf[row] = o;
             } else {
                 if (tid < n_valid) {
                     const int64_t row = (int64_t)tile * PT + tid;
@@ -1692,6 +1722,7 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
 // launchers, one translation unit per kernel family (co-compiled instantiations of one template perturb each other's register
 // allocation and scheduling by several percent -- CDNA guide, methodology rule 19 -- so the hot kernels are compiled alone)
 void sdfr_launch_fwd_f32_512(const MlpParams& P, int64_t n, bool save_masks, hipStream_t s);    // mlp_fwd32.hip
+void sdfr_launch_fwd_f32_512_ordered(const MlpParams& P, int64_t n, const int32_t* order, int64_t order_rows, hipStream_t s);
 int sdfr_fwd_f32_512_np();                                                                        // its point tiles per workgroup
 void sdfr_launch_fwd_f16_512(const MlpParams& P, int64_t n, bool save_masks, hipStream_t s);   // mlp_fwd16.hip
 void sdfr_launch_fwd_f16_512_half_tiles(const MlpParams& P, int64_t n, hipStream_t s);          // mlp_fwd16.hip (64-row tiles, masks)
