@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 410        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 411        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -43,7 +43,7 @@ extern "C" {
  * sdfr_point_extents; 405: frame ingest, sdfr_depth_map, sdfr_match_boxes and sdfr_css_input; 406: the CSS output head, sdfr_css_head and
  * sdfr_css_latent; 407: its training losses and gradients, sdfr_css_head_loss and sdfr_css_latent_loss; 408: the road-plane removal, sdfr_lidar_normals_ws_bytes,
  * sdfr_lidar_normals and sdfr_depth_map_masked; 409: the training-crop augmentation, sdfr_augment; 410: the grid forward with the caller's tile order,
- * sdfr_grid_tile_order and sdfr_mlp_forward_ordered).  A caller built
+ * sdfr_grid_tile_order and sdfr_mlp_forward_ordered; 411: triangle meshes, sdfr_mesh_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -904,6 +904,36 @@ int sdfr_css_head_loss(const float* x_u, const float* x_v, const float* x_w, con
  * [B][3].  workspace: at least B * 3092 bytes of device memory (8-byte aligned).  Two launches. */
 int sdfr_css_latent_loss(const float* x4, int B, int C, int h, int w, const float* w_lat, const float* b_lat, const float* latent_gt,
                          float* loss, float* dx4, float* dw_lat, float* db_lat, void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
+ * Triangle meshes of SDF samples on a regular lattice (csrc/mesh.hip; no counterpart in the reference, which never leaves the shape as
+ * geometry).  Marching tetrahedra on the Kuhn subdivision -- six tetrahedra per cell walking from corner 000 to 111 one axis at a time, in
+ * the order of the permutations of (x, y, z) --, the vertices shared between triangles welded.  DESIGN.md ("Meshes") states the rules.
+ *   lattice   R points per axis, 2 <= R <= 256, x_i = float32(-1 + 2 i / (R - 1)) evaluated in float64, row = (ix R + iy) R + iz;
+ *             B * R^3 < 2^31
+ *   inside    sdf < 0; an exact 0 and a NaN are outside
+ *   vertices  one per lattice edge p -> p + d (d in {0,1}^3 \ 0, the class: d as a binary number with x the high bit) whose ends differ,
+ *             at p_a + t (p_b - p_a) with t = s_a / (s_a - s_b), float32, multiply and add rounded separately (a NaN t becomes 1/2); ordered
+ *             by (row of p, class)
+ *   triangles ordered by (row of the cell's low corner, tetrahedron, triangle), wound so that the normal points from inside to outside;
+ *             indices are local to the shape.  Triangles of zero area (exact zeros at lattice points) are kept; a surface that leaves the
+ *             cube stays open there.
+ * No atomics: the same bits on every run, and a shape's output does not depend on the batch around it.
+ */
+/* bytes of the workspace of the count / emit pair for B shapes (-1: R or B out of range) */
+int64_t sdfr_mesh_ws_bytes(int R, int B);
+/* inputs[b][j][:] = latents[b][0..L) || xyz of lattice row row0 + j, for b < B, j < nrows: the decoder's input rows of a chunk of the lattice.
+ * latents [B][L], inputs [B][nrows][L + 3]. */
+int sdfr_mesh_lattice_inputs(const float* latents, int L, int R, int B, int64_t row0, int64_t nrows, float* inputs, void* stream);
+/* sdf [B][R^3] -> nv[b], nt[b] (device int32): shape b's vertex and triangle counts.  The workspace keeps the per-point records and the
+ * scanned block offsets for the emit call.  Two launches, no host synchronisation. */
+int sdfr_mesh_count(const float* sdf, int R, int B, int32_t* nv, int32_t* nt, void* workspace, int64_t workspace_bytes, void* stream);
+/* vertices [cap_v][3] float32 (lattice frame) and faces [cap_t][3] int32 of all shapes: shape b's at voff[b] .. voff[b + 1] and
+ * toff[b] .. toff[b + 1].  voff, toff: HOST int64 [B + 1], the exclusive sums of the counts the caller read after the count call over the
+ * same sdf and workspace.  Fails before any launch if voff[B] > cap_v or toff[B] > cap_t, and never writes outside a shape's own range.  The
+ * offsets travel to the device in two small copies, so the call cannot be captured in a graph. */
+int sdfr_mesh_emit(const float* sdf, int R, int B, const int64_t* voff, const int64_t* toff, void* workspace, int64_t workspace_bytes,
+                   float* vertices, int64_t cap_v, int32_t* faces, int64_t cap_t, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

@@ -18,13 +18,14 @@ import torch.nn.functional as F
 from .. import _lib
 from ..frame import (NECESSARY_KEYS, _as_tensor, css_inputs_many, depth_map, frame_dict, init_params_many, labels_many, match_boxes,
                      reproject_many, road_free_depth_map, surfaces_many)
+from ..mesh import meshes_many
 from .optimizer import optimize_many
 from .pose import PoseEstimator
 from .refinement import adjust_intrinsics_crop, get_annos
 
 
 def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, iters, weights, pose_type='kabsch', scale=2.0, rendering_area=32,
-                 sampler='device', seed=0, keys=None, optimize_kwargs=None, return_stages=False):
+                 sampler='device', seed=0, keys=None, optimize_kwargs=None, return_stages=False, mesh_resolution=None):
     """One frame from crops to the evaluator's dict.
 
     annotations: per annotation a dict with 'bbox' [l, t, r, b] (the crop's box in the image), 'color' (the crop of the image, (H, W, 3)),
@@ -38,7 +39,11 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
     nearest-neighbour interpolation, filter=True) -> the surface of the CSS latents -> estimate_many -> init_params_many -> optimize_many
     -> labels_many -> frame_dict.  Annotations without a RANSAC pose are dropped, as the reference `continue`s.
     Returns (frame_estimations, kept): the {key: ndarray} dict of the frame's labels and the indices of the annotations behind its rows
-    (and, with return_stages, a dict of every stage's results)."""
+    (and, with return_stages, a dict of every stage's results).
+    mesh_resolution (needs return_stages=True): the stages gain 'meshes', one sdflabel_amd.mesh.Mesh per kept annotation in the camera frame
+    (mesh.meshes_many at that lattice resolution, polished, then Mesh.to_camera with the label's own cam_T).  None: nothing changes."""
+    if mesh_resolution is not None and not return_stages:
+        raise ValueError("refine_frame: mesh_resolution needs return_stages=True (the meshes are returned among the stages)")
     device = grid.points.device
     precision = grid.points.dtype
     n = len(annotations)
@@ -61,16 +66,27 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
                             iters, dsdf, grid, device, weights, **(optimize_kwargs or {}))
     labels = labels_many(dsdf, grid, refined, world_to_cam, [annotations[i]['bbox'] for i in kept])
     est = frame_dict(labels)
+    meshes = None
+    if mesh_resolution is not None:
+        live = [j for j, lab in enumerate(labels) if lab is not None]
+        meshes = meshes_many(dsdf, [refined[j]['latent'].to(precision) if torch.is_tensor(refined[j]['latent']) else refined[j]['latent']
+                                    for j in live], resolution=mesh_resolution)
+        for m, j in zip(meshes, live):
+            m.scale, m.cam_T = float(labels[j][1]._s), labels[j][2]              # the scale and matrix the label itself was built with
+        meshes = [m.to_camera() for m in meshes]
     kept = [i for i, lab in zip(kept, labels) if lab is not None]
     if return_stages:
-        return est, kept, {'crop_sizes': sizes, 'intrinsics': intr, 'off_intrinsics': off, 'lidar': lidar, 'nocs_3d': nocs3d, 'surfaces': surf,
-                           'poses': poses, 'params': refined, 'labels': labels}
+        stages = {'crop_sizes': sizes, 'intrinsics': intr, 'off_intrinsics': off, 'lidar': lidar, 'nocs_3d': nocs3d, 'surfaces': surf,
+                  'poses': poses, 'params': refined, 'labels': labels}
+        if meshes is not None:
+            stages['meshes'] = meshes
+        return est, kept, stages
     return est, kept
 
 
 def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_annos='', label_type='gt', maskrcnn_labels=None, lidar=None,
                   css_batch=None, pose_type='kabsch', scale=2.0, rendering_area=32, sampler='device', seed=0, keys=None, optimize_kwargs=None,
-                  return_stages=False, remove_road=False):
+                  return_stages=False, remove_road=False, mesh_resolution=None):
     """One KITTI sample from the loaded frame to the evaluator's dicts: the body of the reference's frame loop (refine_css.py:94-245).
 
     sample: {'image' (H, W, 3) float32 BGR in 0 ... 1, 'orig_cam' 3x3, 'world_to_cam' 4x4, 'annos' {'easy', 'medium', 'hard'} and 'depth'
@@ -103,7 +119,10 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
     original boxes, and including the annotations that were dropped, as the reference appends before it skips; a key of alpha, bbox,
     dimensions, location, rotation_y, score that no annotation carries is left out, where the reference stores an empty array).  With return_stages a
     fourth value: refine_frame's stages (rows: the annotations that passed the matching) plus 'annos', 'boxes', 'match', 'depth', 'css_input',
-    'css_input_orig', 'nocs_pred', 'latents'.  keys, if given, holds one RANSAC key per selected annotation."""
+    'css_input_orig', 'nocs_pred', 'latents'.  keys, if given, holds one RANSAC key per selected annotation.
+    mesh_resolution: refine_frame's (needs return_stages=True; the stages gain 'meshes')."""
+    if mesh_resolution is not None and not return_stages:
+        raise ValueError("refine_sample: mesh_resolution needs return_stages=True (the meshes are returned among the stages)")
     if label_type not in ('gt', 'rcnn', 'maskrcnn'):
         raise ValueError("refine_sample: label_type must be 'gt', 'rcnn' or 'maskrcnn'")
     device = grid.points.device
@@ -170,7 +189,7 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
     annotations = [{'bbox': lboxes[j], 'color': colors[j], 'depth': depths[j], 'nocs_pred': nocs[j]} for j in range(len(live))]
     out = refine_frame(annotations, dsdf, grid, latents, K_orig, sample['world_to_cam'], iters, weights, pose_type=pose_type, scale=scale,
                        rendering_area=rendering_area, sampler=sampler, seed=seed, keys=None if keys is None else [keys[i] for i in live],
-                       optimize_kwargs=optimize_kwargs, return_stages=return_stages)
+                       optimize_kwargs=optimize_kwargs, return_stages=return_stages, mesh_resolution=mesh_resolution)
     kept = [live[j] for j in out[1]]
     if return_stages:
         stages = dict(out[2], annos=annos, boxes=boxes, match=match, css_input=css_in, css_input_orig=css_vis, nocs_pred=nocs, latents=latents,
