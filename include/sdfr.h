@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 411        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 412        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -43,7 +43,8 @@ extern "C" {
  * sdfr_point_extents; 405: frame ingest, sdfr_depth_map, sdfr_match_boxes and sdfr_css_input; 406: the CSS output head, sdfr_css_head and
  * sdfr_css_latent; 407: its training losses and gradients, sdfr_css_head_loss and sdfr_css_latent_loss; 408: the road-plane removal, sdfr_lidar_normals_ws_bytes,
  * sdfr_lidar_normals and sdfr_depth_map_masked; 409: the training-crop augmentation, sdfr_augment; 410: the grid forward with the caller's tile order,
- * sdfr_grid_tile_order and sdfr_mlp_forward_ordered; 411: triangle meshes, sdfr_mesh_*).  A caller built
+ * sdfr_grid_tile_order and sdfr_mlp_forward_ordered; 411: triangle meshes, sdfr_mesh_*; 412: verification of
+ * refined labels, sdfr_mesh_raster and sdfr_verify_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -934,6 +935,47 @@ int sdfr_mesh_count(const float* sdf, int R, int B, int32_t* nv, int32_t* nt, vo
  * offsets travel to the device in two small copies, so the call cannot be captured in a graph. */
 int sdfr_mesh_emit(const float* sdf, int R, int B, const int64_t* voff, const int64_t* toff, void* workspace, int64_t workspace_bytes,
                    float* vertices, int64_t cap_v, int32_t* faces, int64_t cap_t, void* stream);
+
+/*
+ * Verification of refined autolabels (csrc/verify.hip; the reference's published code stops before this stage).  DESIGN.md ("Verification")
+ * states the rules; csrc/verify_cells.h is the arithmetic, which also compiles for the host.  All pointers are device pointers except K.
+ *
+ * sdfr_mesh_raster: B ragged camera-frame meshes, each rendered into its own window of a W x H image.
+ *   vertices float32 [V][3], faces int32 [T][3] with indices local to the mesh, voff / toff int64 [B + 1] the meshes' vertex and triangle
+ *   offsets, windows int32 [B][4] the half-open integer windows l, t, r, b inside the image (an empty one is legal), poff int64 [B + 1] the
+ *   windows' pixel offsets: poff[b + 1] - poff[b] = (r - l)(b - t), pixel (x, y) of window b at poff[b] + (y - t)(r - l) + (x - l).
+ *   K: HOST double[4] = fx, fy, cx, cy.  z_min >= 0.
+ *   projection   float64 from the float32 vertex: u = fx (X / Z) + cx, v = fy (Y / Z) + cy, every operation rounded separately
+ *   sample       pixel (x, y) is sampled at the point (x, y)
+ *   coverage     E_i = (a.u - x)(b.v - y) - (a.v - y)(b.u - x) for the edge (a, b) opposite vertex i, A2 = (u1 - u0)(v2 - v0) - (v1 - v0)(u2 - u0);
+ *                covered when A2 != 0 and all E_i sign(A2) >= 0: inclusive edges, both windings
+ *   depth        S = (E0 + E1) + E2, depth = (float)(S / ((E0 / Z0 + E1 / Z1) + E2 / Z2)); a depth that is not a positive finite float is no cover
+ *   winner       the minimum of (bits(depth) << 32) | triangle index: nearest, and on an exact tie the lowest index
+ *   skipped      a triangle with a non-finite vertex or projection; one with a vertex at Z <= z_min (flag bit 0); one with a face index outside
+ *                its mesh (flag bit 1).  A mesh whose window leaves the image or does not match its pixel offsets is skipped whole (flag bit 1).
+ *   outputs      per window pixel mask uint8 (0 / 1), depth float32 (0 where uncovered), triangle int32 (-1 where uncovered), each [P];
+ *                flags int32 [B].  keys: workspace of 8 P bytes (8-byte aligned).
+ * The pixel box of a triangle is clamped to the window in floating point before it becomes integers: no vertex value gives a write or a loop
+ * outside the window.  Integer atomic minimum on the keys, then a resolve launch: the same bits on every run.  Three launches, no memset.
+ */
+int sdfr_mesh_raster(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const int64_t* voff, const int64_t* toff,
+                     const int32_t* windows, const int64_t* poff, int64_t P, int B, int W, int H, const double* K, float z_min, void* keys,
+                     uint8_t* mask, float* depth, int32_t* triangle, int32_t* flags, void* stream);
+/* counts int32 [B][8] per window: covered area; the tight half-open box l, t, r, b of the covered pixels (zeros for none); the label's area and
+ * the intersection area (zeros when label_mask, uint8 [P] laid out like mask, is NULL); flag bit 1 if the window is unusable (then all zeros).
+ * One workgroup per window, integer sums. */
+int sdfr_verify_mask_counts(const uint8_t* mask, const uint8_t* label_mask, const int32_t* windows, const int64_t* poff, int64_t P, int B, int W,
+                            int H, int32_t* counts, void* stream);
+/* The decoder's input rows of camera-frame lidar points: rows[j] = latents[a] || x for point row0 + j, a its annotation, j < nrows.
+ * points float32 [N][3], ptoff int64 [B + 1] the annotations' point offsets (ptoff[0] = 0, ptoff[B] = N), pose float32 [B][6] = cos(yaw),
+ * sin(yaw), trans x y z, scale (the label's own float32 values), latents [B][L] (raw).  x = diag(1, -1, 1) rot_yaw^T (p / scale - trans) in
+ * float64, rounded once to float32: the inverse of Mesh.to_camera / assemble_labels.  in_cube uint8 [N]: 1 when x lies in [-1, 1]^3. */
+int sdfr_verify_point_rows(const float* points, int64_t N, const int64_t* ptoff, int B, const float* pose, const float* latents, int L,
+                           int64_t row0, int64_t nrows, float* rows, uint8_t* in_cube, void* stream);
+/* counts int32 [B][3] = n_pts, n_cube, n_band per annotation from the decoder's values sdf [N] at those rows: a point is in the band when it
+ * is in the cube and fabsf(sdf) * scale < band in float32.  One workgroup per annotation, integer sums. */
+int sdfr_verify_band_counts(const float* sdf, const uint8_t* in_cube, int64_t N, const int64_t* ptoff, int B, const float* pose, float band,
+                            int32_t* counts, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

@@ -19,13 +19,14 @@ from .. import _lib
 from ..frame import (NECESSARY_KEYS, _as_tensor, css_inputs_many, depth_map, frame_dict, init_params_many, labels_many, match_boxes,
                      reproject_many, road_free_depth_map, surfaces_many)
 from ..mesh import meshes_many
+from ..verify import label_windows, verify_many
 from .optimizer import optimize_many
 from .pose import PoseEstimator
 from .refinement import adjust_intrinsics_crop, get_annos
 
 
 def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, iters, weights, pose_type='kabsch', scale=2.0, rendering_area=32,
-                 sampler='device', seed=0, keys=None, optimize_kwargs=None, return_stages=False, mesh_resolution=None):
+                 sampler='device', seed=0, keys=None, optimize_kwargs=None, return_stages=False, mesh_resolution=None, verify=None):
     """One frame from crops to the evaluator's dict.
 
     annotations: per annotation a dict with 'bbox' [l, t, r, b] (the crop's box in the image), 'color' (the crop of the image, (H, W, 3)),
@@ -41,9 +42,18 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
     Returns (frame_estimations, kept): the {key: ndarray} dict of the frame's labels and the indices of the annotations behind its rows
     (and, with return_stages, a dict of every stage's results).
     mesh_resolution (needs return_stages=True): the stages gain 'meshes', one sdflabel_amd.mesh.Mesh per kept annotation in the camera frame
-    (mesh.meshes_many at that lattice resolution, polished, then Mesh.to_camera with the label's own cam_T).  None: nothing changes."""
+    (mesh.meshes_many at that lattice resolution, polished, then Mesh.to_camera with the label's own cam_T).  None: nothing changes.
+    verify (needs return_stages=True): True, or a dict of verify.verify_many's keyword arguments.  The stages gain 'verify', one verdict
+    dict per kept annotation: the refined shape -- meshed at mesh_resolution, or at 64 when that is None -- is rendered into the
+    annotation's box and compared with it, and the annotation's lidar cloud (stages['lidar'][i][0]) is counted in the band round the
+    surface.  The dict may also hold 'image_size' (W, H), to which the windows are clipped -- without it the image is taken just large
+    enough for the grown boxes -- and 'label_masks', one per ANNOTATION (of its box's shape, or None).  Nothing is filtered: est and kept
+    are the bits of the call without verify, and the caller decides what to drop.  One more host read.  None: nothing changes."""
     if mesh_resolution is not None and not return_stages:
         raise ValueError("refine_frame: mesh_resolution needs return_stages=True (the meshes are returned among the stages)")
+    if verify is not None and verify is not False and not return_stages:
+        raise ValueError("refine_frame: verify needs return_stages=True (the verdicts are returned among the stages)")
+    verify = None if verify is False else ({} if verify is True else verify)
     device = grid.points.device
     precision = grid.points.dtype
     n = len(annotations)
@@ -67,26 +77,39 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
     labels = labels_many(dsdf, grid, refined, world_to_cam, [annotations[i]['bbox'] for i in kept])
     est = frame_dict(labels)
     meshes = None
-    if mesh_resolution is not None:
+    if mesh_resolution is not None or verify is not None:
         live = [j for j, lab in enumerate(labels) if lab is not None]
         meshes = meshes_many(dsdf, [refined[j]['latent'].to(precision) if torch.is_tensor(refined[j]['latent']) else refined[j]['latent']
-                                    for j in live], resolution=mesh_resolution)
+                                    for j in live], resolution=64 if mesh_resolution is None else mesh_resolution)
         for m, j in zip(meshes, live):
             m.scale, m.cam_T = float(labels[j][1]._s), labels[j][2]              # the scale and matrix the label itself was built with
         meshes = [m.to_camera() for m in meshes]
+    verdicts = None
+    if verify is not None:
+        kw = dict(verify)
+        boxes = [annotations[kept[j]]['bbox'] for j in live]
+        label_masks = kw.pop('label_masks', None)
+        size = kw.pop('image_size', None)
+        if size is None and live:                            # just large enough for the grown boxes: nothing is clipped on the right / at the bottom
+            far = label_windows(boxes, (1 << 30, 1 << 30), kw.get('margin', 0.25))[1]
+            size = (max(1, int(far[:, 2].max())), max(1, int(far[:, 3].max())))
+        verdicts = verify_many(dsdf, [refined[j] for j in live], meshes, [lidar[kept[j]][0] for j in live], K_orig, boxes, size or (1, 1),
+                               label_masks=None if label_masks is None else [label_masks[kept[j]] for j in live], **kw)
     kept = [i for i, lab in zip(kept, labels) if lab is not None]
     if return_stages:
         stages = {'crop_sizes': sizes, 'intrinsics': intr, 'off_intrinsics': off, 'lidar': lidar, 'nocs_3d': nocs3d, 'surfaces': surf,
                   'poses': poses, 'params': refined, 'labels': labels}
-        if meshes is not None:
+        if meshes is not None and mesh_resolution is not None:
             stages['meshes'] = meshes
+        if verdicts is not None:
+            stages['verify'] = verdicts
         return est, kept, stages
     return est, kept
 
 
 def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_annos='', label_type='gt', maskrcnn_labels=None, lidar=None,
                   css_batch=None, pose_type='kabsch', scale=2.0, rendering_area=32, sampler='device', seed=0, keys=None, optimize_kwargs=None,
-                  return_stages=False, remove_road=False, mesh_resolution=None):
+                  return_stages=False, remove_road=False, mesh_resolution=None, verify=None):
     """One KITTI sample from the loaded frame to the evaluator's dicts: the body of the reference's frame loop (refine_css.py:94-245).
 
     sample: {'image' (H, W, 3) float32 BGR in 0 ... 1, 'orig_cam' 3x3, 'world_to_cam' 4x4, 'annos' {'easy', 'medium', 'hard'} and 'depth'
@@ -120,7 +143,11 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
     dimensions, location, rotation_y, score that no annotation carries is left out, where the reference stores an empty array).  With return_stages a
     fourth value: refine_frame's stages (rows: the annotations that passed the matching) plus 'annos', 'boxes', 'match', 'depth', 'css_input',
     'css_input_orig', 'nocs_pred', 'latents'.  keys, if given, holds one RANSAC key per selected annotation.
-    mesh_resolution: refine_frame's (needs return_stages=True; the stages gain 'meshes')."""
+    mesh_resolution: refine_frame's (needs return_stages=True; the stages gain 'meshes').
+    verify: refine_frame's (needs return_stages=True; the stages gain 'verify').  The windows are clipped to the sample's image, and with
+    label_type='maskrcnn' the matched detector masks are the label masks, so 'iou_mask' is filled."""
+    if verify is not None and verify is not False and not return_stages:
+        raise ValueError("refine_sample: verify needs return_stages=True (the verdicts are returned among the stages)")
     if mesh_resolution is not None and not return_stages:
         raise ValueError("refine_sample: mesh_resolution needs return_stages=True (the meshes are returned among the stages)")
     if label_type not in ('gt', 'rcnn', 'maskrcnn'):
@@ -187,9 +214,13 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
                     nocs.append(uvw[j] / 255.)
                     latents.append(lat[j].to(precision))
     annotations = [{'bbox': lboxes[j], 'color': colors[j], 'depth': depths[j], 'nocs_pred': nocs[j]} for j in range(len(live))]
+    if verify is not None and verify is not False:
+        verify = dict({} if verify is True else verify, image_size=(W, H))
+        if masks is not None:
+            verify.setdefault('label_masks', masks)
     out = refine_frame(annotations, dsdf, grid, latents, K_orig, sample['world_to_cam'], iters, weights, pose_type=pose_type, scale=scale,
                        rendering_area=rendering_area, sampler=sampler, seed=seed, keys=None if keys is None else [keys[i] for i in live],
-                       optimize_kwargs=optimize_kwargs, return_stages=return_stages, mesh_resolution=mesh_resolution)
+                       optimize_kwargs=optimize_kwargs, return_stages=return_stages, mesh_resolution=mesh_resolution, verify=verify)
     kept = [live[j] for j in out[1]]
     if return_stages:
         stages = dict(out[2], annos=annos, boxes=boxes, match=match, css_input=css_in, css_input_orig=css_vis, nocs_pred=nocs, latents=latents,
