@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 412        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 413        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -44,7 +44,7 @@ extern "C" {
  * sdfr_css_latent; 407: its training losses and gradients, sdfr_css_head_loss and sdfr_css_latent_loss; 408: the road-plane removal, sdfr_lidar_normals_ws_bytes,
  * sdfr_lidar_normals and sdfr_depth_map_masked; 409: the training-crop augmentation, sdfr_augment; 410: the grid forward with the caller's tile order,
  * sdfr_grid_tile_order and sdfr_mlp_forward_ordered; 411: triangle meshes, sdfr_mesh_*; 412: verification of
- * refined labels, sdfr_mesh_raster and sdfr_verify_*).  A caller built
+ * refined labels, sdfr_mesh_raster and sdfr_verify_*; 413: the export of training crops, sdfr_crop_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -976,6 +976,42 @@ int sdfr_verify_point_rows(const float* points, int64_t N, const int64_t* ptoff,
  * is in the cube and fabsf(sdf) * scale < band in float32.  One workgroup per annotation, integer sums. */
 int sdfr_verify_band_counts(const float* sdf, const uint8_t* in_cube, int64_t N, const int64_t* ptoff, int B, const float* pose, float band,
                             int32_t* counts, void* stream);
+
+/*
+ * Export of CSS training crops from rasterised autolabels (csrc/crops.hip; DESIGN.md "Training crops").  csrc/crop_cells.h is the
+ * arithmetic, which also compiles for the host.  All pointers are device pointers except K.  windows / poff / P, voff / toff, K and z_min are
+ * sdfr_mesh_raster's, and mask / depth / triangle its packed outputs.
+ *
+ * sdfr_crop_owner: owner int32 [P] per window pixel of a frame's B rasters: -1 where the annotation's own mask does not cover, its own index
+ *   where it is the nearest there, otherwise the index of the nearest occluder.  The key of annotation b at a pixel is
+ *   (bits(depth) << 32) | b and the minimum wins: the nearest, and on an exact tie the lowest index.  An annotation counts at a pixel only if
+ *   its window contains the pixel and its mask covers it there: AN OCCLUDER IS SEEN ONLY INSIDE ITS OWN WINDOW.  A window that leaves the
+ *   image or does not match its offsets is ignored and its pixels get -1.  One launch.
+ */
+int sdfr_crop_owner(const uint8_t* mask, const float* depth, const int32_t* windows, const int64_t* poff, int64_t P, int B, int W, int H,
+                    int32_t* owner, void* stream);
+/* Per annotation a half-open box l, t, r, b (boxes int32 [B][4]) inside its window; outputs packed by qoff int64 [B + 1], the exclusive sum of
+ * the box areas (Q = qoff[B]): box pixel (x, y) of annotation b at qoff[b] + (y - t)(r - l) + (x - l).
+ *   uvw uint8 [Q][3]   where the pixel's winning triangle is not -1 and (owner is NULL or owner == b): with E_i the rasteriser's edge values of
+ *                      the winning triangle at the pixel, q_i = E_i / Z_i, D = (q0 + q1) + q2, n_k = (q0 a0[k] + q1 a1[k]) + q2 a2[k] (float64,
+ *                      every operation rounded separately), val = (n_k / D + 1) 127.5 -> 0 for val <= 0 or NaN, 255 for val >= 255, else
+ *                      rint(val); three zero bytes become (0, 0, 1).  a_i: attributes float32 [V][3] at the triangle's vertices (the
+ *                      lattice-frame positions: NOCS).  Zeros elsewhere.  owner == NULL: occlusion off.
+ *   rgb uint8 [Q][3]   optional (rgb and colors both or neither): colors float32 [Q][3] is the annotation's BGR colour crop packed the same
+ *                      way; the bytes are rintf(255 v) in float32 clamped to 0 ... 255 (NaN: 0), written in RGB order.
+ *   flags int32 [B]    VERIFY_FLAG_INVALID (2) for an annotation whose window leaves the image, whose box leaves its window, whose offsets do
+ *                      not fit the arrays, or whose triangle image holds an index outside the mesh other than -1 (or a triangle the
+ *                      rasteriser would have skipped); all pixels of such an annotation are zeroed.
+ * Nothing is read or written out of bounds for any values in the arrays.  Three launches, no memset, no host synchronisation. */
+int sdfr_crop_export(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const float* attributes, const int64_t* voff,
+                     const int64_t* toff, const int32_t* windows, const int64_t* poff, int64_t P, const int32_t* triangle, const int32_t* owner,
+                     const int32_t* boxes, const int64_t* qoff, int64_t Q, const float* colors, int B, int W, int H, const double* K, float z_min,
+                     uint8_t* uvw, uint8_t* rgb, int32_t* flags, void* stream);
+/* counts int32 [B][4] per annotation: box pixels, covered (mask != 0 inside the box), visible (covered and owner == b; owner NULL: all covered),
+ * and the flag word: flags[b] (sdfr_crop_export's, may be NULL) or-ed with bit 1 if window and box do not fit, in which case the three
+ * counts are 0.  One workgroup per annotation, integer sums in a fixed tree. */
+int sdfr_crop_counts(const uint8_t* mask, const int32_t* owner, const int32_t* windows, const int64_t* poff, int64_t P, const int32_t* boxes,
+                     const int64_t* qoff, int64_t Q, const int32_t* flags, int B, int W, int H, int32_t* counts, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

@@ -33,11 +33,13 @@ def lattice_points(R, device="cpu"):
 class Mesh:
     """One shape's triangle mesh.  `.vertices` float32 [V][3], `.faces` int32 [T][3] and `.normals` float32 [V][3] (or None) are device
     tensors; `*_numpy()` fetch them once, on demand.  `.scale` and `.cam_T` (4x4, as frame.assemble_labels builds it) take the lattice frame
-    to the camera frame: to_camera().  `.sdf` holds the [R][R][R] samples when they were asked for."""
+    to the camera frame: to_camera().  `.sdf` holds the [R][R][R] samples when they were asked for.  A camera-frame mesh made by to_camera()
+    carries the lattice-frame vertices it came from as `.lattice_vertices` (same order: per-vertex NOCS attributes); None otherwise."""
 
     def __init__(self, vertices, faces, normals=None, scale=None, cam_T=None, sdf=None, frame="lattice"):
         self.vertices, self.faces, self.normals = vertices, faces, normals
         self.scale, self.cam_T, self.sdf, self.frame = scale, cam_T, sdf, frame
+        self.lattice_vertices = None
         self._host = {}
 
     def _fetch(self, name):
@@ -92,7 +94,9 @@ class Mesh:
         mirrored = float(np.linalg.det(np.asarray(self.cam_T, dtype=np.float64)[:3, :3])) < 0
         faces = self.faces[:, [0, 2, 1]].contiguous() if mirrored else self.faces
         nrm = None if self.normals is None else (self.normals.double() @ A.t()).float()
-        return Mesh(v, faces, nrm, scale=self.scale, cam_T=self.cam_T, sdf=self.sdf, frame="camera")
+        out = Mesh(v, faces, nrm, scale=self.scale, cam_T=self.cam_T, sdf=self.sdf, frame="camera")
+        out.lattice_vertices = self.vertices                   # the vertex order is kept: the NOCS attributes of the camera-frame mesh
+        return out
 
     def save(self, path, drop_degenerate=False):
         """binary little-endian PLY (with normals when the mesh has them) or OBJ, by extension.  Host code."""

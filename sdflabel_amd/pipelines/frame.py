@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from .. import _lib
 from ..frame import (NECESSARY_KEYS, _as_tensor, css_inputs_many, depth_map, frame_dict, init_params_many, labels_many, match_boxes,
                      reproject_many, road_free_depth_map, surfaces_many)
+from ..export import crops_many
 from ..mesh import meshes_many
 from ..verify import label_windows, verify_many
 from .optimizer import optimize_many
@@ -25,8 +26,14 @@ from .pose import PoseEstimator
 from .refinement import adjust_intrinsics_crop, get_annos
 
 
+def _grown_size(boxes, margin):
+    """an image (W, H) just large enough for the boxes grown by `margin`: nothing is clipped on the right / at the bottom"""
+    far = label_windows(boxes, (1 << 30, 1 << 30), margin)[1]
+    return max(1, int(far[:, 2].max())), max(1, int(far[:, 3].max()))
+
+
 def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, iters, weights, pose_type='kabsch', scale=2.0, rendering_area=32,
-                 sampler='device', seed=0, keys=None, optimize_kwargs=None, return_stages=False, mesh_resolution=None, verify=None):
+                 sampler='device', seed=0, keys=None, optimize_kwargs=None, return_stages=False, mesh_resolution=None, verify=None, crops=None):
     """One frame from crops to the evaluator's dict.
 
     annotations: per annotation a dict with 'bbox' [l, t, r, b] (the crop's box in the image), 'color' (the crop of the image, (H, W, 3)),
@@ -48,12 +55,21 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
     annotation's box and compared with it, and the annotation's lidar cloud (stages['lidar'][i][0]) is counted in the band round the
     surface.  The dict may also hold 'image_size' (W, H), to which the windows are clipped -- without it the image is taken just large
     enough for the grown boxes -- and 'label_masks', one per ANNOTATION (of its box's shape, or None).  Nothing is filtered: est and kept
-    are the bits of the call without verify, and the caller decides what to drop.  One more host read.  None: nothing changes."""
+    are the bits of the call without verify, and the caller decides what to drop.  One more host read.  None: nothing changes.
+    crops (needs return_stages=True): True, or a dict of export.crops_many's keyword arguments (and 'image_size', as for verify).  The stages
+    gain 'crops', one export.Crop per kept annotation: the NOCS bytes of the refined shape -- the same meshes as verify's, at
+    mesh_resolution, or at 64 when that is None -- in the annotation's box, the annotations occluding each other, and the RGB bytes of the
+    annotation's 'color' crop.  Each crop also carries what a CropWriter entry needs: `.latent` (the raw refined latent), `.intrinsics` (the
+    frame's K) and `.extrinsics` (the label's cam_T); pipelines.export_crops.export_frame writes them.  No host read; est, kept and every
+    other stage are the bits of the call without crops.  None: nothing changes."""
     if mesh_resolution is not None and not return_stages:
         raise ValueError("refine_frame: mesh_resolution needs return_stages=True (the meshes are returned among the stages)")
     if verify is not None and verify is not False and not return_stages:
         raise ValueError("refine_frame: verify needs return_stages=True (the verdicts are returned among the stages)")
+    if crops is not None and crops is not False and not return_stages:
+        raise ValueError("refine_frame: crops needs return_stages=True (the crops are returned among the stages)")
     verify = None if verify is False else ({} if verify is True else verify)
+    crops = None if crops is False else ({} if crops is True else crops)
     device = grid.points.device
     precision = grid.points.dtype
     n = len(annotations)
@@ -77,7 +93,7 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
     labels = labels_many(dsdf, grid, refined, world_to_cam, [annotations[i]['bbox'] for i in kept])
     est = frame_dict(labels)
     meshes = None
-    if mesh_resolution is not None or verify is not None:
+    if mesh_resolution is not None or verify is not None or crops is not None:
         live = [j for j, lab in enumerate(labels) if lab is not None]
         meshes = meshes_many(dsdf, [refined[j]['latent'].to(precision) if torch.is_tensor(refined[j]['latent']) else refined[j]['latent']
                                     for j in live], resolution=64 if mesh_resolution is None else mesh_resolution)
@@ -90,11 +106,20 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
         boxes = [annotations[kept[j]]['bbox'] for j in live]
         label_masks = kw.pop('label_masks', None)
         size = kw.pop('image_size', None)
-        if size is None and live:                            # just large enough for the grown boxes: nothing is clipped on the right / at the bottom
-            far = label_windows(boxes, (1 << 30, 1 << 30), kw.get('margin', 0.25))[1]
-            size = (max(1, int(far[:, 2].max())), max(1, int(far[:, 3].max())))
+        if size is None and live:
+            size = _grown_size(boxes, kw.get('margin', 0.25))
         verdicts = verify_many(dsdf, [refined[j] for j in live], meshes, [lidar[kept[j]][0] for j in live], K_orig, boxes, size or (1, 1),
                                label_masks=None if label_masks is None else [label_masks[kept[j]] for j in live], **kw)
+    crop_list = None
+    if crops is not None:
+        kw = dict(crops)
+        boxes = [annotations[kept[j]]['bbox'] for j in live]
+        size = kw.pop('image_size', None)
+        if size is None and live:
+            size = _grown_size(boxes, kw.get('margin', 0.25))
+        crop_list = crops_many(meshes, K_orig, boxes, size or (1, 1), colors=[annotations[kept[j]]['color'] for j in live], **kw)
+        for c, j in zip(crop_list, live):
+            c.latent, c.intrinsics, c.extrinsics = refined[j]['latent'], K_orig, labels[j][2]
     kept = [i for i, lab in zip(kept, labels) if lab is not None]
     if return_stages:
         stages = {'crop_sizes': sizes, 'intrinsics': intr, 'off_intrinsics': off, 'lidar': lidar, 'nocs_3d': nocs3d, 'surfaces': surf,
@@ -103,13 +128,15 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
             stages['meshes'] = meshes
         if verdicts is not None:
             stages['verify'] = verdicts
+        if crop_list is not None:
+            stages['crops'] = crop_list
         return est, kept, stages
     return est, kept
 
 
 def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_annos='', label_type='gt', maskrcnn_labels=None, lidar=None,
                   css_batch=None, pose_type='kabsch', scale=2.0, rendering_area=32, sampler='device', seed=0, keys=None, optimize_kwargs=None,
-                  return_stages=False, remove_road=False, mesh_resolution=None, verify=None):
+                  return_stages=False, remove_road=False, mesh_resolution=None, verify=None, crops=None):
     """One KITTI sample from the loaded frame to the evaluator's dicts: the body of the reference's frame loop (refine_css.py:94-245).
 
     sample: {'image' (H, W, 3) float32 BGR in 0 ... 1, 'orig_cam' 3x3, 'world_to_cam' 4x4, 'annos' {'easy', 'medium', 'hard'} and 'depth'
@@ -145,7 +172,11 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
     'css_input_orig', 'nocs_pred', 'latents'.  keys, if given, holds one RANSAC key per selected annotation.
     mesh_resolution: refine_frame's (needs return_stages=True; the stages gain 'meshes').
     verify: refine_frame's (needs return_stages=True; the stages gain 'verify').  The windows are clipped to the sample's image, and with
-    label_type='maskrcnn' the matched detector masks are the label masks, so 'iou_mask' is filled."""
+    label_type='maskrcnn' the matched detector masks are the label masks, so 'iou_mask' is filled.
+    crops: refine_frame's (needs return_stages=True; the stages gain 'crops').  The windows are clipped to the sample's image and the RGB
+    bytes come from the sample's image."""
+    if crops is not None and crops is not False and not return_stages:
+        raise ValueError("refine_sample: crops needs return_stages=True (the crops are returned among the stages)")
     if verify is not None and verify is not False and not return_stages:
         raise ValueError("refine_sample: verify needs return_stages=True (the verdicts are returned among the stages)")
     if mesh_resolution is not None and not return_stages:
@@ -218,9 +249,11 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
         verify = dict({} if verify is True else verify, image_size=(W, H))
         if masks is not None:
             verify.setdefault('label_masks', masks)
+    if crops is not None and crops is not False:
+        crops = dict({} if crops is True else crops, image_size=(W, H))
     out = refine_frame(annotations, dsdf, grid, latents, K_orig, sample['world_to_cam'], iters, weights, pose_type=pose_type, scale=scale,
                        rendering_area=rendering_area, sampler=sampler, seed=seed, keys=None if keys is None else [keys[i] for i in live],
-                       optimize_kwargs=optimize_kwargs, return_stages=return_stages, mesh_resolution=mesh_resolution, verify=verify)
+                       optimize_kwargs=optimize_kwargs, return_stages=return_stages, mesh_resolution=mesh_resolution, verify=verify, crops=crops)
     kept = [live[j] for j in out[1]]
     if return_stages:
         stages = dict(out[2], annos=annos, boxes=boxes, match=match, css_input=css_in, css_input_orig=css_vis, nocs_pred=nocs, latents=latents,
