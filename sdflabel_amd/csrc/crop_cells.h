@@ -19,19 +19,13 @@ VERIFY_HD uint8_t crop_byte(double val) {
 }
 
 // The three NOCS bytes of a COVERED pixel (x, y) of triangle T (verify_tri_setup for the raster's window, K and z_min) with the float32
-// attributes a0, a1, a2 [3] of its vertices.  du, dv, E are verify_pixel_key's expressions; q_i = E_i / z_i; D = (q0 + q1) + q2;
+// attributes a0, a1, a2 [3] of its vertices.  E is verify_edges', as the rasteriser's own; q_i = E_i / z_i; D = (q0 + q1) + q2;
 // n_k = (q0 a0[k] + q1 a1[k]) + q2 a2[k], every product rounded on its own; c_k = n_k / D; val = (c_k + 1) 127.5.  Three zero bytes become
 // (0, 0, 1): the loader's mask u + v + w > 0 is then exactly the set of labelled pixels.
 VERIFY_HD void crop_shade(const VerifyTri* T, int x, int y, const float* a0, const float* a1, const float* a2, uint8_t* out) {
-    const double px = (double)x, py = (double)y;
-    double du[3], dv[3], q[3];
-    for (int i = 0; i < 3; ++i) du[i] = T->u[i] - px, dv[i] = T->v[i] - py;
-    for (int i = 0; i < 3; ++i) {                       // edge (a, b) opposite vertex i
-        const int a = (i + 1) % 3, b = (i + 2) % 3;
-        const double m0 = du[a] * dv[b], m1 = dv[a] * du[b];
-        const double E = m0 - m1;
-        q[i] = E / T->z[i];
-    }
+    double E[3], q[3];
+    verify_edges(T, x, y, E);
+    for (int i = 0; i < 3; ++i) q[i] = E[i] / T->z[i];
     const double D = (q[0] + q[1]) + q[2];
     for (int k = 0; k < 3; ++k) {
         const double t0 = q[0] * (double)a0[k], t1 = q[1] * (double)a1[k], t2 = q[2] * (double)a2[k];
@@ -58,12 +52,6 @@ VERIFY_HD uint64_t crop_owner_key(float depth, uint32_t b) {
     return (uint64_t)bits << 32 | (uint64_t)b;
 }
 
-// the window [l, t, r, b) lies inside the W x H image and its pixels are exactly off[0] .. off[1] of an array of P
-VERIFY_HD bool crop_window_ok(const int32_t* w, const int64_t* off, int64_t P, int W, int H) {
-    if (!(0 <= w[0] && w[0] <= w[2] && w[2] <= W && 0 <= w[1] && w[1] <= w[3] && w[3] <= H)) return false;
-    return off[0] >= 0 && off[1] <= P && off[1] - off[0] == (int64_t)(w[2] - w[0]) * (w[3] - w[1]);
-}
-
 // the half-open box lies inside the window and its pixels are exactly off[0] .. off[1] of an array of Q
 VERIFY_HD bool crop_box_ok(const int32_t* box, const int32_t* w, const int64_t* off, int64_t Q) {
     if (!(w[0] <= box[0] && box[0] <= box[2] && box[2] <= w[2] && w[1] <= box[1] && box[1] <= box[3] && box[3] <= w[3])) return false;
@@ -82,9 +70,9 @@ VERIFY_HD int32_t crop_owner_pixel(const uint8_t* mask, const float* depth, cons
     for (int c = 0; c < B; ++c) {
         if (c == b) continue;
         const int32_t* w = windows + 4 * c;
-        if (!crop_window_ok(w, poff + c, P, W, H)) continue;
+        if (!verify_window_ok(w, poff + c, P, W, H)) continue;
         if (!(w[0] <= x && x < w[2] && w[1] <= y && y < w[3])) continue;
-        const int64_t j = poff[c] + (int64_t)(y - w[1]) * (w[2] - w[0]) + (x - w[0]);
+        const int64_t j = verify_window_pixel(w, poff[c], x, y);
         if (mask[j] == 0) continue;
         const uint64_t key = crop_owner_key(depth[j], (uint32_t)c);
         if (key < best) best = key;
@@ -92,26 +80,17 @@ VERIFY_HD int32_t crop_owner_pixel(const uint8_t* mask, const float* depth, cons
     return (int32_t)(uint32_t)(best & 0xffffffffull);
 }
 
-// Everything the export needs to know about one ragged batch; all pointers as the entry points take them.
-struct CropArgs {
-    const float* vertices;       // [V][3] camera frame
-    const int32_t* faces;        // [T][3], indices local to the mesh
+// The raster's batch and what the export adds to it; all pointers as the entry points take them.
+struct CropArgs : RasterArgs {
     const float* attributes;     // [V][3] per-vertex attributes (lattice-frame positions)
-    const int64_t* voff;         // [B + 1]
-    const int64_t* toff;         // [B + 1]
-    const int32_t* windows;      // [B][4] l, t, r, b
-    const int64_t* poff;         // [B + 1]
     const int32_t* boxes;        // [B][4] l, t, r, b inside the window
     const int64_t* qoff;         // [B + 1]
-    int B, W, H;
-    int64_t V, T, P, Q;
-    double K[4];
-    float z_min;
+    int64_t Q;
 };
 
 // annotation b's window, box and offsets fit together and stay inside what the caller allocated
 VERIFY_HD bool crop_anno_ok(const CropArgs* a, int b) {
-    return crop_window_ok(a->windows + 4 * b, a->poff + b, a->P, a->W, a->H) && crop_box_ok(a->boxes + 4 * b, a->windows + 4 * b, a->qoff + b, a->Q) &&
+    return verify_window_ok(a->windows + 4 * b, a->poff + b, a->P, a->W, a->H) && crop_box_ok(a->boxes + 4 * b, a->windows + 4 * b, a->qoff + b, a->Q) &&
            crop_range_ok(a->voff + b, a->V) && crop_range_ok(a->toff + b, a->T);
 }
 
@@ -131,14 +110,14 @@ VERIFY_HD int crop_export_pixel(const CropArgs* a, const int32_t* triangle, cons
     const int64_t local = g - a->qoff[b];
     const int bw = box[2] - box[0];
     const int x = box[0] + (int)(local % bw), y = box[1] + (int)(local / bw);
-    const int64_t i = a->poff[b] + (int64_t)(y - w[1]) * (w[2] - w[0]) + (x - w[0]);         // inside poff[b] .. poff[b + 1]: the box is inside the window
+    const int64_t i = verify_window_pixel(w, a->poff[b], x, y);                            // inside poff[b] .. poff[b + 1]: the box is inside the window
     *window_pixel = i;
     const int32_t tri = triangle[i];
     if (tri == -1) return 0;
     const int64_t t0 = a->toff[b], nt = a->toff[b + 1] - t0, v0 = a->voff[b], nv = a->voff[b + 1] - v0;
     if (tri < 0 || tri >= nt) return VERIFY_FLAG_INVALID;
     const int32_t* f = a->faces + 3 * (t0 + tri);
-    if (!(f[0] >= 0 && f[1] >= 0 && f[2] >= 0 && f[0] < nv && f[1] < nv && f[2] < nv)) return VERIFY_FLAG_INVALID;
+    if (!verify_face_ok(f, nv)) return VERIFY_FLAG_INVALID;
     if (owner && owner[i] != b) return 0;
     VerifyTri T;
     // a triangle the rasteriser would have skipped cannot have won a pixel: the triangle image does not belong to this mesh

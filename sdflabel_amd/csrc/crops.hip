@@ -14,18 +14,16 @@
 #include "sdfr_common.h"
 #include "crop_cells.h"
 
-#define CROP_BLOCK 256
-
 namespace {
 
-__global__ __launch_bounds__(CROP_BLOCK) void sdfr_crop_owner_kernel(const uint8_t* __restrict__ mask, const float* __restrict__ depth,
+__global__ __launch_bounds__(VERIFY_BLOCK) void sdfr_crop_owner_kernel(const uint8_t* __restrict__ mask, const float* __restrict__ depth,
                                                                      const int32_t* __restrict__ windows, const int64_t* __restrict__ poff,
                                                                      int64_t P, int B, int W, int H, int32_t* __restrict__ owner) {
-    const int64_t i = (int64_t)blockIdx.x * CROP_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * VERIFY_BLOCK + threadIdx.x;
     if (i >= P) return;
     const int b = verify_owner(poff, B, i);
     const int32_t* w = windows + 4 * b;
-    if (!crop_window_ok(w, poff + b, P, W, H) || i < poff[b] || i >= poff[b + 1]) {        // the pixel belongs to no usable window
+    if (!verify_window_ok(w, poff + b, P, W, H) || i < poff[b] || i >= poff[b + 1]) {        // the pixel belongs to no usable window
         owner[i] = -1;
         return;
     }
@@ -36,16 +34,16 @@ __global__ __launch_bounds__(CROP_BLOCK) void sdfr_crop_owner_kernel(const uint8
 
 // flag words: 0, or VERIFY_FLAG_INVALID for an annotation whose window, box and offsets do not fit (a kernel, not a memset: every entry
 // point may be captured into a graph, sdfr_common.h)
-__global__ __launch_bounds__(CROP_BLOCK) void sdfr_crop_init_kernel(CropArgs a, int32_t* __restrict__ flags) {
-    const int b = blockIdx.x * CROP_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(VERIFY_BLOCK) void sdfr_crop_init_kernel(CropArgs a, int32_t* __restrict__ flags) {
+    const int b = blockIdx.x * VERIFY_BLOCK + threadIdx.x;
     if (b < a.B) flags[b] = crop_anno_ok(&a, b) ? 0 : VERIFY_FLAG_INVALID;
 }
 
-__global__ __launch_bounds__(CROP_BLOCK) void sdfr_crop_export_kernel(CropArgs a, const int32_t* __restrict__ triangle,
+__global__ __launch_bounds__(VERIFY_BLOCK) void sdfr_crop_export_kernel(CropArgs a, const int32_t* __restrict__ triangle,
                                                                       const int32_t* __restrict__ owner, const float* __restrict__ colors,
                                                                       uint8_t* __restrict__ uvw, uint8_t* __restrict__ rgb,
                                                                       int32_t* __restrict__ flags) {
-    const int64_t g = (int64_t)blockIdx.x * CROP_BLOCK + threadIdx.x;
+    const int64_t g = (int64_t)blockIdx.x * VERIFY_BLOCK + threadIdx.x;
     if (g >= a.Q) return;
     uint8_t out[3];
     int b;
@@ -59,9 +57,9 @@ __global__ __launch_bounds__(CROP_BLOCK) void sdfr_crop_export_kernel(CropArgs a
 }
 
 // after the export: the pixels of an annotation whose flag word says invalid are zeroed (a bad triangle index is found by one pixel only)
-__global__ __launch_bounds__(CROP_BLOCK) void sdfr_crop_scrub_kernel(CropArgs a, const int32_t* __restrict__ flags, uint8_t* __restrict__ uvw,
+__global__ __launch_bounds__(VERIFY_BLOCK) void sdfr_crop_scrub_kernel(CropArgs a, const int32_t* __restrict__ flags, uint8_t* __restrict__ uvw,
                                                                      uint8_t* __restrict__ rgb) {
-    const int64_t g = (int64_t)blockIdx.x * CROP_BLOCK + threadIdx.x;
+    const int64_t g = (int64_t)blockIdx.x * VERIFY_BLOCK + threadIdx.x;
     if (g >= a.Q) return;
     const int b = verify_owner(a.qoff, a.B, g);
     if (!(flags[b] & VERIFY_FLAG_INVALID)) return;
@@ -69,25 +67,12 @@ __global__ __launch_bounds__(CROP_BLOCK) void sdfr_crop_scrub_kernel(CropArgs a,
     if (rgb) rgb[3 * g] = rgb[3 * g + 1] = rgb[3 * g + 2] = 0;
 }
 
-// sum of one int per thread over the workgroup, in a fixed tree; the result is valid in every thread
-__device__ __forceinline__ int crop_block_sum(int v, int* sh) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    sh[t] = v;
-    __syncthreads();
-    for (int o = CROP_BLOCK / 2; o > 0; o >>= 1) {
-        if (t < o) sh[t] = sh[t] + sh[t + o];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-__global__ __launch_bounds__(CROP_BLOCK) void sdfr_crop_counts_kernel(CropArgs a, const uint8_t* __restrict__ mask, const int32_t* __restrict__ owner,
+__global__ __launch_bounds__(VERIFY_BLOCK) void sdfr_crop_counts_kernel(CropArgs a, const uint8_t* __restrict__ mask, const int32_t* __restrict__ owner,
                                                                       const int32_t* __restrict__ flags, int32_t* __restrict__ counts) {
-    __shared__ int sh[CROP_BLOCK];
+    __shared__ int sh[VERIFY_BLOCK];
     const int b = blockIdx.x;
     int32_t* o = counts + CROP_COUNTS * b;
-    const bool fits = crop_window_ok(a.windows + 4 * b, a.poff + b, a.P, a.W, a.H) && crop_box_ok(a.boxes + 4 * b, a.windows + 4 * b, a.qoff + b, a.Q);
+    const bool fits = verify_window_ok(a.windows + 4 * b, a.poff + b, a.P, a.W, a.H) && crop_box_ok(a.boxes + 4 * b, a.windows + 4 * b, a.qoff + b, a.Q);
     const int32_t word = (flags ? flags[b] : 0) | (fits ? 0 : VERIFY_FLAG_INVALID);
     if (word & VERIFY_FLAG_INVALID) {                        // uniform over the workgroup
         if (threadIdx.x < CROP_COUNTS) o[threadIdx.x] = threadIdx.x == CROP_COUNTS - 1 ? word : 0;
@@ -95,30 +80,22 @@ __global__ __launch_bounds__(CROP_BLOCK) void sdfr_crop_counts_kernel(CropArgs a
     }
     const int32_t* w = a.windows + 4 * b;
     const int32_t* box = a.boxes + 4 * b;
-    const int bw = box[2] - box[0], ww = w[2] - w[0];
+    const int bw = box[2] - box[0];
     const int n = bw * (box[3] - box[1]);                    // at most the image: below 2^31
     int covered = 0, visible = 0;
-    for (int i = threadIdx.x; i < n; i += CROP_BLOCK) {
+    for (int i = threadIdx.x; i < n; i += VERIFY_BLOCK) {
         const int x = box[0] + i % bw, y = box[1] + i / bw;
-        const int64_t at = a.poff[b] + (int64_t)(y - w[1]) * ww + (x - w[0]);
+        const int64_t at = verify_window_pixel(w, a.poff[b], x, y);
         const bool c = mask[at] != 0;
         covered += c;
         visible += c && (!owner || owner[at] == b);
     }
-    covered = crop_block_sum(covered, sh);
-    visible = crop_block_sum(visible, sh);
+    covered = verify_block_reduce<0>(covered, sh);
+    visible = verify_block_reduce<0>(visible, sh);
     if (threadIdx.x == 0) o[0] = n, o[1] = covered, o[2] = visible, o[3] = word;
 }
 
-void crop_args(CropArgs* a, const float* vertices, int64_t V, const int32_t* faces, int64_t T, const float* attributes, const int64_t* voff,
-               const int64_t* toff, const int32_t* windows, const int64_t* poff, int64_t P, const int32_t* boxes, const int64_t* qoff, int64_t Q, int B,
-               int W, int H, const double* K, float z_min) {
-    *a = CropArgs{vertices, faces, attributes, voff, toff, windows, poff, boxes, qoff, B, W, H, V, T, P, Q, {0, 0, 0, 0}, z_min};
-    if (K)
-        for (int i = 0; i < 4; ++i) a->K[i] = K[i];
-}
-
-unsigned crop_blocks(int64_t n) { return (unsigned)((n + CROP_BLOCK - 1) / CROP_BLOCK); }
+unsigned crop_blocks(int64_t n) { return (unsigned)((n + VERIFY_BLOCK - 1) / VERIFY_BLOCK); }
 
 }  // namespace
 
@@ -128,7 +105,7 @@ extern "C" int sdfr_crop_owner(const uint8_t* mask, const float* depth, const in
     SDFR_REQUIRE(P >= 0 && P <= (int64_t)B * W * H, "sdfr_crop_owner: P = %lld out of range (P <= B W H)", (long long)P);
     if (B == 0 || P == 0) return SDFR_OK;
     SDFR_REQUIRE(mask && depth && windows && poff && owner, "sdfr_crop_owner: NULL pointer");
-    hipLaunchKernelGGL(sdfr_crop_owner_kernel, dim3(crop_blocks(P)), dim3(CROP_BLOCK), 0, (hipStream_t)stream, mask, depth, windows, poff, P, B, W, H,
+    hipLaunchKernelGGL(sdfr_crop_owner_kernel, dim3(crop_blocks(P)), dim3(VERIFY_BLOCK), 0, (hipStream_t)stream, mask, depth, windows, poff, P, B, W, H,
                        owner);
     SDFR_LAUNCH_CHECK();
     return SDFR_OK;
@@ -149,15 +126,14 @@ extern "C" int sdfr_crop_export(const float* vertices, int64_t V, const int32_t*
     SDFR_REQUIRE(voff && toff && windows && poff && boxes && qoff && flags, "sdfr_crop_export: NULL pointer");
     SDFR_REQUIRE((V == 0 || (vertices && attributes)) && (T == 0 || faces), "sdfr_crop_export: NULL mesh");
     SDFR_REQUIRE((P == 0 || triangle) && (Q == 0 || uvw), "sdfr_crop_export: NULL triangle image or output");
-    CropArgs a;
-    crop_args(&a, vertices, V, faces, T, attributes, voff, toff, windows, poff, P, boxes, qoff, Q, B, W, H, K, z_min);
+    const CropArgs a = {raster_args(vertices, V, faces, T, voff, toff, windows, poff, P, B, W, H, K, z_min), attributes, boxes, qoff, Q};
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(sdfr_crop_init_kernel, dim3(crop_blocks(B)), dim3(CROP_BLOCK), 0, s, a, flags);
+    hipLaunchKernelGGL(sdfr_crop_init_kernel, dim3(crop_blocks(B)), dim3(VERIFY_BLOCK), 0, s, a, flags);
     SDFR_LAUNCH_CHECK();
     if (Q > 0) {
-        hipLaunchKernelGGL(sdfr_crop_export_kernel, dim3(crop_blocks(Q)), dim3(CROP_BLOCK), 0, s, a, triangle, owner, colors, uvw, rgb, flags);
+        hipLaunchKernelGGL(sdfr_crop_export_kernel, dim3(crop_blocks(Q)), dim3(VERIFY_BLOCK), 0, s, a, triangle, owner, colors, uvw, rgb, flags);
         SDFR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sdfr_crop_scrub_kernel, dim3(crop_blocks(Q)), dim3(CROP_BLOCK), 0, s, a, (const int32_t*)flags, uvw, rgb);
+        hipLaunchKernelGGL(sdfr_crop_scrub_kernel, dim3(crop_blocks(Q)), dim3(VERIFY_BLOCK), 0, s, a, (const int32_t*)flags, uvw, rgb);
         SDFR_LAUNCH_CHECK();
     }
     return SDFR_OK;
@@ -171,9 +147,8 @@ extern "C" int sdfr_crop_counts(const uint8_t* mask, const int32_t* owner, const
                  (long long)P, (long long)Q);
     if (B == 0) return SDFR_OK;
     SDFR_REQUIRE(windows && poff && boxes && qoff && counts && (P == 0 || mask), "sdfr_crop_counts: NULL pointer");
-    CropArgs a;
-    crop_args(&a, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, windows, poff, P, boxes, qoff, Q, B, W, H, nullptr, 0.0f);
-    hipLaunchKernelGGL(sdfr_crop_counts_kernel, dim3((unsigned)B), dim3(CROP_BLOCK), 0, (hipStream_t)stream, a, mask, owner, flags, counts);
+    const CropArgs a = {raster_args(nullptr, 0, nullptr, 0, nullptr, nullptr, windows, poff, P, B, W, H, nullptr, 0.0f), nullptr, boxes, qoff, Q};
+    hipLaunchKernelGGL(sdfr_crop_counts_kernel, dim3((unsigned)B), dim3(VERIFY_BLOCK), 0, (hipStream_t)stream, a, mask, owner, flags, counts);
     SDFR_LAUNCH_CHECK();
     return SDFR_OK;
 }

@@ -16,31 +16,8 @@
 #include "verify_cells.h"
 
 #define VERIFY_SMALL 32          // pixel boxes up to this many pixels are walked by the triangle's own lane
-#define VERIFY_BLOCK 256
 
 namespace {
-
-struct RasterArgs {
-    const float* vertices;       // [V][3]
-    const int32_t* faces;        // [T][3], indices local to the mesh
-    const int64_t* voff;         // [B + 1]
-    const int64_t* toff;         // [B + 1]
-    const int32_t* windows;      // [B][4] l, t, r, b
-    const int64_t* poff;         // [B + 1]
-    int B, W, H;
-    int64_t V, T, P;
-    double K[4];
-    float z_min;
-};
-
-// the window and the offsets of mesh b fit together and stay inside what the caller allocated
-__device__ __forceinline__ bool verify_mesh_ok(const RasterArgs& a, int b, int64_t P) {
-    const int32_t* w = a.windows + 4 * b;
-    const int l = w[0], t = w[1], r = w[2], bt = w[3];
-    if (!(0 <= l && l <= r && r <= a.W && 0 <= t && t <= bt && bt <= a.H)) return false;
-    const int64_t p0 = a.poff[b], p1 = a.poff[b + 1];
-    return p0 >= 0 && p1 <= P && p1 - p0 == (int64_t)(r - l) * (bt - t);
-}
 
 // set up global triangle g of the ragged batch for its mesh's window; returns the status and the mesh; flags are raised here
 __device__ __forceinline__ int verify_load_tri(const RasterArgs& a, int64_t g, VerifyTri* T, int* mesh, int32_t* local, int32_t* flags) {
@@ -48,14 +25,14 @@ __device__ __forceinline__ int verify_load_tri(const RasterArgs& a, int64_t g, V
     *mesh = b;
     *local = (int32_t)(g - a.toff[b]);
     const int64_t v0 = a.voff[b], nv = a.voff[b + 1] - v0;
-    const int32_t i0 = a.faces[3 * g], i1 = a.faces[3 * g + 1], i2 = a.faces[3 * g + 2];
-    const bool idx_ok = v0 >= 0 && a.voff[b + 1] <= a.V && i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < nv && i1 < nv && i2 < nv;
-    if (!idx_ok || !verify_mesh_ok(a, b, a.P)) {
+    const int32_t f[3] = {a.faces[3 * g], a.faces[3 * g + 1], a.faces[3 * g + 2]};
+    const int32_t* w = a.windows + 4 * b;
+    const bool idx_ok = v0 >= 0 && a.voff[b + 1] <= a.V && verify_face_ok(f, nv);
+    if (!idx_ok || !verify_window_ok(w, a.poff + b, a.P, a.W, a.H)) {
         atomicOr(&flags[b], VERIFY_FLAG_INVALID);
         return VERIFY_TRI_SKIP;
     }
-    const int32_t* w = a.windows + 4 * b;
-    const int st = verify_tri_setup(a.vertices + 3 * (v0 + i0), a.vertices + 3 * (v0 + i1), a.vertices + 3 * (v0 + i2), a.K, a.z_min, w[0], w[1],
+    const int st = verify_tri_setup(a.vertices + 3 * (v0 + f[0]), a.vertices + 3 * (v0 + f[1]), a.vertices + 3 * (v0 + f[2]), a.K, a.z_min, w[0], w[1],
                                     w[2], w[3], T);
     if (st == VERIFY_TRI_BEHIND) atomicOr(&flags[b], VERIFY_FLAG_BEHIND);
     return st;
@@ -65,10 +42,8 @@ __device__ __forceinline__ void verify_put(const RasterArgs& a, int b, const Ver
                                            unsigned long long* keys) {
     const uint64_t key = verify_pixel_key(&T, x, y, (uint32_t)local);
     if (key == VERIFY_NO_KEY) return;
-    const int32_t* w = a.windows + 4 * b;
-    // (x, y) is inside the window (verify_tri_setup clamped the box) and the window's pixels are poff[b] .. poff[b + 1] (verify_mesh_ok)
-    const int64_t at = a.poff[b] + (int64_t)(y - w[1]) * (w[2] - w[0]) + (x - w[0]);
-    atomicMin(&keys[at], (unsigned long long)key);
+    // (x, y) is inside the window (verify_tri_setup clamped the box) and the window's pixels are poff[b] .. poff[b + 1] (verify_window_ok)
+    atomicMin(&keys[verify_window_pixel(a.windows + 4 * b, a.poff[b], x, y)], (unsigned long long)key);
 }
 
 // keys to "no cover", flags to 0 (a kernel, not a memset: every entry point may be captured into a graph, sdfr_common.h)
@@ -121,33 +96,16 @@ __global__ __launch_bounds__(VERIFY_BLOCK) void sdfr_mesh_resolve_kernel(const u
     verify_resolve((uint64_t)keys[i], &mask[i], &depth[i], &tri[i]);
 }
 
-// sum (or min / max) of one int per thread over the workgroup, in a fixed tree; the result is valid in every thread
-template <int OP>
-__device__ __forceinline__ int verify_block_reduce(int v, int* sh) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    sh[t] = v;
-    __syncthreads();
-    for (int o = VERIFY_BLOCK / 2; o > 0; o >>= 1) {
-        if (t < o) {
-            const int x = sh[t], y = sh[t + o];
-            sh[t] = OP == 0 ? x + y : OP == 1 ? (x < y ? x : y) : (x > y ? x : y);
-        }
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 __global__ __launch_bounds__(VERIFY_BLOCK) void sdfr_verify_mask_counts_kernel(const uint8_t* __restrict__ mask, const uint8_t* __restrict__ label,
                                                                                RasterArgs a, int32_t* __restrict__ out) {
     __shared__ int sh[VERIFY_BLOCK];
     const int b = blockIdx.x;
     int32_t* o = out + 8 * b;
-    if (!verify_mesh_ok(a, b, a.P)) {                        // uniform over the workgroup
+    const int32_t* w = a.windows + 4 * b;
+    if (!verify_window_ok(w, a.poff + b, a.P, a.W, a.H)) {   // uniform over the workgroup
         if (threadIdx.x < 8) o[threadIdx.x] = threadIdx.x == 7 ? VERIFY_FLAG_INVALID : 0;
         return;
     }
-    const int32_t* w = a.windows + 4 * b;
     const int l = w[0], t = w[1], ww = w[2] - w[0];
     const int n = ww * (w[3] - w[1]);
     const uint8_t* m = mask + a.poff[b];
@@ -219,14 +177,6 @@ __global__ __launch_bounds__(VERIFY_BLOCK) void sdfr_verify_band_counts_kernel(c
     }
 }
 
-bool raster_args(RasterArgs* a, const float* vertices, int64_t V, const int32_t* faces, int64_t T, const int64_t* voff, const int64_t* toff,
-                 const int32_t* windows, const int64_t* poff, int64_t P, int B, int W, int H, const double* K, float z_min) {
-    *a = RasterArgs{vertices, faces, voff, toff, windows, poff, B, W, H, V, T, P, {0, 0, 0, 0}, z_min};
-    if (K)
-        for (int i = 0; i < 4; ++i) a->K[i] = K[i];
-    return true;
-}
-
 }  // namespace
 
 extern "C" int sdfr_mesh_raster(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const int64_t* voff, const int64_t* toff,
@@ -241,8 +191,7 @@ extern "C" int sdfr_mesh_raster(const float* vertices, int64_t V, const int32_t*
     SDFR_REQUIRE(voff && toff && windows && poff && flags, "sdfr_mesh_raster: NULL pointer");
     SDFR_REQUIRE((V == 0 || vertices) && (T == 0 || faces), "sdfr_mesh_raster: NULL mesh");
     SDFR_REQUIRE(P == 0 || (keys && mask && depth && triangle), "sdfr_mesh_raster: NULL output");
-    RasterArgs a;
-    raster_args(&a, vertices, V, faces, T, voff, toff, windows, poff, P, B, W, H, K, z_min);
+    const RasterArgs a = raster_args(vertices, V, faces, T, voff, toff, windows, poff, P, B, W, H, K, z_min);
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_init = P > B ? P : B;
     hipLaunchKernelGGL(sdfr_mesh_raster_init_kernel, dim3((unsigned)((n_init + VERIFY_BLOCK - 1) / VERIFY_BLOCK)), dim3(VERIFY_BLOCK), 0, s,
@@ -267,8 +216,7 @@ extern "C" int sdfr_verify_mask_counts(const uint8_t* mask, const uint8_t* label
     SDFR_REQUIRE(P >= 0 && P <= (int64_t)B * W * H, "sdfr_verify_mask_counts: P = %lld out of range (P <= B W H)", (long long)P);
     if (B == 0) return SDFR_OK;
     SDFR_REQUIRE(windows && poff && counts && (P == 0 || mask), "sdfr_verify_mask_counts: NULL pointer");
-    RasterArgs a;
-    raster_args(&a, nullptr, 0, nullptr, 0, nullptr, nullptr, windows, poff, P, B, W, H, nullptr, 0.0f);
+    const RasterArgs a = raster_args(nullptr, 0, nullptr, 0, nullptr, nullptr, windows, poff, P, B, W, H, nullptr, 0.0f);
     hipLaunchKernelGGL(sdfr_verify_mask_counts_kernel, dim3((unsigned)B), dim3(VERIFY_BLOCK), 0, (hipStream_t)stream, mask, label_mask, a, counts);
     SDFR_LAUNCH_CHECK();
     return SDFR_OK;

@@ -2,6 +2,8 @@
 // Everything here is a plain function of one triangle, one pixel or one point, compiled for the device by verify.hip and for the host by
 // tests/verify_host/verify_host.cpp, which loops over every triangle, pixel and point and is compared with the numpy restatement
 // (tests/_verify_ref.py) bit for bit.  Both translation units are compiled with -ffp-contract=off: every operation rounds separately.
+// It is also the header of everything that reads the packed rasters: crop_cells.h (crops.hip, tests/export_host/export_host.cpp) includes it
+// for RasterArgs, the window and face predicates, the window-pixel index, the edge functions and the workgroup reduction.
 //
 // Rasteriser: float32 camera-frame vertices, float64 arithmetic.  u = fx (X / Z) + cx, v = fy (Y / Z) + cy; pixel (x, y) is sampled at the
 // point (x, y); edges are inclusive, both windings count; the winner of a pixel is the minimum of (bits(depth) << 32) | triangle index.
@@ -71,17 +73,25 @@ VERIFY_HD int verify_tri_setup(const float* p0, const float* p1, const float* p2
     return VERIFY_TRI_OK;
 }
 
-// The triangle's key at pixel (x, y), or VERIFY_NO_KEY where it does not cover the pixel or its depth there is not a positive finite float.
-VERIFY_HD uint64_t verify_pixel_key(const VerifyTri* T, int x, int y, uint32_t tri) {
+// The edge functions of pixel (x, y): E[i] belongs to the edge (a, b) opposite vertex i, every product rounded on its own.  The rasteriser's
+// cover test and depth and the export's interpolation (crop_cells.h) both start from these values.
+VERIFY_HD void verify_edges(const VerifyTri* T, int x, int y, double* E) {
     const double px = (double)x, py = (double)y;
-    double du[3], dv[3], E[3];
+    double du[3], dv[3];
     for (int i = 0; i < 3; ++i) du[i] = T->u[i] - px, dv[i] = T->v[i] - py;
-    for (int i = 0; i < 3; ++i) {                       // edge (a, b) opposite vertex i
+    for (int i = 0; i < 3; ++i) {
         const int a = (i + 1) % 3, b = (i + 2) % 3;
         const double m0 = du[a] * dv[b], m1 = dv[a] * du[b];
         E[i] = m0 - m1;
-        if (!(E[i] * T->sgn >= 0.0)) return VERIFY_NO_KEY;
     }
+}
+
+// The triangle's key at pixel (x, y), or VERIFY_NO_KEY where it does not cover the pixel or its depth there is not a positive finite float.
+VERIFY_HD uint64_t verify_pixel_key(const VerifyTri* T, int x, int y, uint32_t tri) {
+    double E[3];
+    verify_edges(T, x, y, E);
+    for (int i = 0; i < 3; ++i)
+        if (!(E[i] * T->sgn >= 0.0)) return VERIFY_NO_KEY;
     const double S = (E[0] + E[1]) + E[2];
     const double q0 = E[0] / T->z[0], q1 = E[1] / T->z[1], q2 = E[2] / T->z[2];
     const double D = (q0 + q1) + q2;
@@ -134,3 +144,62 @@ VERIFY_HD int verify_owner(const int64_t* off, int n, int64_t g) {
     }
     return lo;
 }
+
+// Everything the rasteriser and the kernels that read its packed output need to know about one ragged batch; all pointers as the entry
+// points take them (NULL / 0 for what a kernel does not read).
+struct RasterArgs {
+    const float* vertices;       // [V][3] camera frame
+    const int32_t* faces;        // [T][3], indices local to the mesh
+    const int64_t* voff;         // [B + 1]
+    const int64_t* toff;         // [B + 1]
+    const int32_t* windows;      // [B][4] l, t, r, b
+    const int64_t* poff;         // [B + 1]
+    int B, W, H;
+    int64_t V, T, P;
+    double K[4];
+    float z_min;
+};
+
+static inline RasterArgs raster_args(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const int64_t* voff, const int64_t* toff,
+                                     const int32_t* windows, const int64_t* poff, int64_t P, int B, int W, int H, const double* K, float z_min) {
+    RasterArgs a = {vertices, faces, voff, toff, windows, poff, B, W, H, V, T, P, {0, 0, 0, 0}, z_min};
+    if (K)
+        for (int i = 0; i < 4; ++i) a.K[i] = K[i];
+    return a;
+}
+
+// the window [l, t, r, b) lies inside the W x H image and its pixels are exactly off[0] .. off[1] of an array of P
+VERIFY_HD bool verify_window_ok(const int32_t* w, const int64_t* off, int64_t P, int W, int H) {
+    const int l = w[0], t = w[1], r = w[2], b = w[3];
+    if (!(0 <= l && l <= r && r <= W && 0 <= t && t <= b && b <= H)) return false;
+    const int64_t p0 = off[0], p1 = off[1];
+    return p0 >= 0 && p1 <= P && p1 - p0 == (int64_t)(r - l) * (b - t);
+}
+
+// the three vertex indices of a face lie inside a mesh of nv vertices
+VERIFY_HD bool verify_face_ok(const int32_t* f, int64_t nv) { return f[0] >= 0 && f[1] >= 0 && f[2] >= 0 && f[0] < nv && f[1] < nv && f[2] < nv; }
+
+// index into the packed rasters of image pixel (x, y) of the window w whose pixels start at poff_b; inside poff[b] .. poff[b + 1] for a
+// pixel inside a window that passed verify_window_ok
+VERIFY_HD int64_t verify_window_pixel(const int32_t* w, int64_t poff_b, int x, int y) { return poff_b + (int64_t)(y - w[1]) * (w[2] - w[0]) + (x - w[0]); }
+
+#if defined(__HIPCC__)
+#define VERIFY_BLOCK 256         // threads per workgroup of every kernel of verify.hip and crops.hip
+
+// sum (OP 0), minimum (1) or maximum (2) of one int per thread over the workgroup, in a fixed tree; the result is valid in every thread
+template <int OP>
+__device__ __forceinline__ int verify_block_reduce(int v, int* sh) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    sh[t] = v;
+    __syncthreads();
+    for (int o = VERIFY_BLOCK / 2; o > 0; o >>= 1) {
+        if (t < o) {
+            const int x = sh[t], y = sh[t + o];
+            sh[t] = OP == 0 ? x + y : OP == 1 ? (x < y ? x : y) : (x > y ? x : y);
+        }
+        __syncthreads();
+    }
+    return sh[0];
+}
+#endif

@@ -9,7 +9,6 @@ CropWriter   the reference's crops folder (crops.json, %05d_rgb.png, %05d_uvw.pn
 The rasteriser of the verification decides which triangle wins a pixel (verify.raster_many); here the lattice-frame positions of that
 triangle's vertices -- the decoder's canonical cube is the NOCS frame -- are interpolated perspective-correctly at the pixel.
 """
-import ctypes
 import json
 import os
 
@@ -19,7 +18,8 @@ import torch
 from . import _lib
 from .mesh import _host
 from .pose import _upload
-from .verify import FLAG_BEHIND, FLAG_INVALID, _intrinsics, _raster_packed, label_windows  # noqa: F401  (the flag bits of Crop.flags)
+from . import verify as _verify
+from .verify import FLAG_BEHIND, FLAG_INVALID, _intrinsics, label_windows  # noqa: F401  (the flag bits of Crop.flags)
 
 
 class Crop:
@@ -54,7 +54,7 @@ def _color_crop(c, lbox, cbox, b, dev):
 
 
 @_lib.traced("crops_many")
-def crops_many(meshes, K, boxes, image_size, colors=None, margin=0.25, occlusion=True, z_min=0.1, attributes=None):
+def crops_many(meshes, K, boxes, image_size, colors=None, margin=0.25, occlusion=True, z_min=0.1, attributes=None, raster=None):
     """Training crops of all annotations of a frame.
 
     meshes: the refined shapes as camera-frame Mesh objects (Mesh.to_camera(), which hands the lattice-frame vertices on as
@@ -62,7 +62,8 @@ def crops_many(meshes, K, boxes, image_size, colors=None, margin=0.25, occlusion
     outward to a half-open integer box and the mesh is rendered into verify.label_windows' window -- that box grown by `margin` and clipped
     to the image, the window verify_many renders into.  The crop is the label box clipped to the image.  colors: per annotation its float32
     BGR colour crop (h, w, 3) with values 0 ... 1, of the label box's shape or the clipped box's, on the device or the host; None: no
-    `.rgb`.  attributes: per mesh a float32 [V][3] array to interpolate instead of `.lattice_vertices`.
+    `.rgb`.  attributes: per mesh a float32 [V][3] array to interpolate instead of `.lattice_vertices`.  raster: the verify.RasterBatch of these
+    meshes in these windows (verify_many's `raster`), to be read instead of rendering again; one made with anything else is refused.
 
     NOCS bytes (DESIGN.md "Training crops"): at the rasteriser's winning triangle the three vertex attributes are interpolated
     perspective-correctly in float64 and coloured as the reference colours NOCS, byte = rint((x + 1) / 2 * 255); a labelled pixel is never
@@ -101,10 +102,10 @@ def crops_many(meshes, K, boxes, image_size, colors=None, margin=0.25, occlusion
     if colors is not None:
         for b, c in enumerate(colors):                       # (shapes only: refused before anything is launched)
             _color_crop(c, lbox[b], box[b], b, None)
-    pk = _raster_packed(meshes, K, win, image_size, z_min)
-    dev = pk["device"]
+    rb = _verify.raster_batch(meshes, K, win, image_size, z_min) if raster is None else raster.require("crops_many", meshes, K, win, image_size, z_min)
+    dev = rb.device
     qoff = np.concatenate([[0], np.cumsum((box[:, 2] - box[:, 0]) * (box[:, 3] - box[:, 1]))]).astype(np.int64)
-    Q, P = int(qoff[-1]), pk["P"]
+    Q, P = int(qoff[-1]), rb.P
     table = _upload(torch.from_numpy(np.concatenate([qoff, box.astype(np.int32).reshape(-1).view(np.int64)])), dev)
     d_qoff, d_box = table[:B + 1], table[B + 1:].view(torch.int32)
     att = [(a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(torch.float32).reshape(-1, 3) for a in att]
@@ -117,22 +118,21 @@ def crops_many(meshes, K, boxes, image_size, colors=None, margin=0.25, occlusion
     owner = torch.empty((P,), dtype=torch.int32, device=dev) if occlusion else None
     flags = torch.empty((B,), dtype=torch.int32, device=dev)
     counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    k4 = (ctypes.c_double * 4)(*_intrinsics(K))
     L, Pt, ck = _lib.lib(), _lib.ptr, _lib.check
-    V, T = int(pk["vertices"].shape[0]), int(pk["faces"].shape[0])
+    V, T = int(rb.vertices.shape[0]), int(rb.faces.shape[0])
     with _lib.guard(dev):
         st = _lib.stream_ptr()
         if occlusion:
-            ck(L.sdfr_crop_owner(Pt(pk["mask"]) if P else None, Pt(pk["depth"]) if P else None, Pt(pk["d_win"]), Pt(pk["d_poff"]), P, B, W, H,
+            ck(L.sdfr_crop_owner(Pt(rb.mask) if P else None, Pt(rb.depth) if P else None, Pt(rb.d_win), Pt(rb.d_poff), P, B, W, H,
                                  Pt(owner) if P else None, st), "sdfr_crop_owner")
-        ck(L.sdfr_crop_export(Pt(pk["vertices"]) if V else None, V, Pt(pk["faces"]) if T else None, T, Pt(attr) if V else None, Pt(pk["d_voff"]),
-                              Pt(pk["d_toff"]), Pt(pk["d_win"]), Pt(pk["d_poff"]), P, Pt(pk["triangle"]) if P else None,
+        ck(L.sdfr_crop_export(Pt(rb.vertices) if V else None, V, Pt(rb.faces) if T else None, T, Pt(attr) if V else None, Pt(rb.d_voff),
+                              Pt(rb.d_toff), Pt(rb.d_win), Pt(rb.d_poff), P, Pt(rb.triangle) if P else None,
                               Pt(owner) if (occlusion and P) else None, Pt(d_box), Pt(d_qoff), Q, Pt(packed) if (packed is not None and Q) else None,
-                              B, W, H, k4, float(z_min), Pt(uvw) if Q else None, Pt(rgb) if (rgb is not None and Q) else None, Pt(flags), st),
+                              B, W, H, rb.k4, float(z_min), Pt(uvw) if Q else None, Pt(rgb) if (rgb is not None and Q) else None, Pt(flags), st),
            "sdfr_crop_export")
-        ck(L.sdfr_crop_counts(Pt(pk["mask"]) if P else None, Pt(owner) if (occlusion and P) else None, Pt(pk["d_win"]), Pt(pk["d_poff"]), P,
+        ck(L.sdfr_crop_counts(Pt(rb.mask) if P else None, Pt(owner) if (occlusion and P) else None, Pt(rb.d_win), Pt(rb.d_poff), P,
                               Pt(d_box), Pt(d_qoff), Q, Pt(flags), B, W, H, Pt(counts), st), "sdfr_crop_counts")
-    word = counts[:, 3] | pk["flags"]
+    word = counts[:, 3] | rb.flags
     out = []
     for b in range(B):
         l, t, r, bt = (int(x) for x in box[b])

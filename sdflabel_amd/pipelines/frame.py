@@ -20,6 +20,7 @@ from ..frame import (NECESSARY_KEYS, _as_tensor, css_inputs_many, depth_map, fra
                      reproject_many, road_free_depth_map, surfaces_many)
 from ..export import crops_many
 from ..mesh import meshes_many
+from .. import verify as _verify
 from ..verify import label_windows, verify_many
 from .optimizer import optimize_many
 from .pose import PoseEstimator
@@ -30,6 +31,25 @@ def _grown_size(boxes, margin):
     """an image (W, H) just large enough for the boxes grown by `margin`: nothing is clipped on the right / at the bottom"""
     far = label_windows(boxes, (1 << 30, 1 << 30), margin)[1]
     return max(1, int(far[:, 2].max())), max(1, int(far[:, 3].max()))
+
+
+def _stage_options(who, return_stages, mesh_resolution, verify, crops):
+    """(mesh_resolution, verify, crops) with False and None as None (off) and True as {}; a stage that is on needs return_stages"""
+    out = []
+    for name, what, v in (("mesh_resolution", "meshes", mesh_resolution), ("verify", "verdicts", verify), ("crops", "crops", crops)):
+        v = None if v is None or v is False else ({} if v is True else v)
+        if v is not None and not return_stages:
+            raise ValueError("%s: %s needs return_stages=True (the %s are returned among the stages)" % (who, name, what))
+        out.append(v)
+    return out
+
+
+def _stage_size(kw, boxes):
+    """a stage's image (W, H), taken out of its keyword arguments: the explicit 'image_size', or just large enough for its grown boxes"""
+    size = kw.pop('image_size', None)
+    if size is None and boxes:
+        size = _grown_size(boxes, kw.get('margin', 0.25))
+    return size or (1, 1)
 
 
 def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, iters, weights, pose_type='kabsch', scale=2.0, rendering_area=32,
@@ -61,15 +81,10 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
     mesh_resolution, or at 64 when that is None -- in the annotation's box, the annotations occluding each other, and the RGB bytes of the
     annotation's 'color' crop.  Each crop also carries what a CropWriter entry needs: `.latent` (the raw refined latent), `.intrinsics` (the
     frame's K) and `.extrinsics` (the label's cam_T); pipelines.export_crops.export_frame writes them.  No host read; est, kept and every
-    other stage are the bits of the call without crops.  None: nothing changes."""
-    if mesh_resolution is not None and not return_stages:
-        raise ValueError("refine_frame: mesh_resolution needs return_stages=True (the meshes are returned among the stages)")
-    if verify is not None and verify is not False and not return_stages:
-        raise ValueError("refine_frame: verify needs return_stages=True (the verdicts are returned among the stages)")
-    if crops is not None and crops is not False and not return_stages:
-        raise ValueError("refine_frame: crops needs return_stages=True (the crops are returned among the stages)")
-    verify = None if verify is False else ({} if verify is True else verify)
-    crops = None if crops is False else ({} if crops is True else crops)
+    other stage are the bits of the call without crops.  None: nothing changes.
+    With verify and crops both on and agreeing on image size, margin and z_min, the frame is rasterised once: one verify.RasterBatch goes to
+    both stages.  Their results are the bits of the separate calls."""
+    mesh_resolution, verify, crops = _stage_options("refine_frame", return_stages, mesh_resolution, verify, crops)
     device = grid.points.device
     precision = grid.points.dtype
     n = len(annotations)
@@ -100,24 +115,21 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
         for m, j in zip(meshes, live):
             m.scale, m.cam_T = float(labels[j][1]._s), labels[j][2]              # the scale and matrix the label itself was built with
         meshes = [m.to_camera() for m in meshes]
-    verdicts = None
+    verdicts, crop_list = None, None
+    if verify is not None or crops is not None:
+        boxes = [annotations[kept[j]]['bbox'] for j in live]
+        vkw, ckw = dict(verify or {}), dict(crops or {})
+        vsize, csize = _stage_size(vkw, boxes), _stage_size(ckw, boxes)
+        made = [(tuple(size), kw.get('margin', 0.25), kw.get('z_min', 0.1)) for size, kw in ((vsize, vkw), (csize, ckw))]
+        shared = None
+        if verify is not None and crops is not None and live and made[0] == made[1]:         # one raster for both stages
+            shared = _verify.raster_batch(meshes, K_orig, label_windows(boxes, vsize, made[0][1])[1], vsize, made[0][2])
     if verify is not None:
-        kw = dict(verify)
-        boxes = [annotations[kept[j]]['bbox'] for j in live]
-        label_masks = kw.pop('label_masks', None)
-        size = kw.pop('image_size', None)
-        if size is None and live:
-            size = _grown_size(boxes, kw.get('margin', 0.25))
-        verdicts = verify_many(dsdf, [refined[j] for j in live], meshes, [lidar[kept[j]][0] for j in live], K_orig, boxes, size or (1, 1),
-                               label_masks=None if label_masks is None else [label_masks[kept[j]] for j in live], **kw)
-    crop_list = None
+        label_masks = vkw.pop('label_masks', None)
+        verdicts = verify_many(dsdf, [refined[j] for j in live], meshes, [lidar[kept[j]][0] for j in live], K_orig, boxes, vsize,
+                               label_masks=None if label_masks is None else [label_masks[kept[j]] for j in live], raster=shared, **vkw)
     if crops is not None:
-        kw = dict(crops)
-        boxes = [annotations[kept[j]]['bbox'] for j in live]
-        size = kw.pop('image_size', None)
-        if size is None and live:
-            size = _grown_size(boxes, kw.get('margin', 0.25))
-        crop_list = crops_many(meshes, K_orig, boxes, size or (1, 1), colors=[annotations[kept[j]]['color'] for j in live], **kw)
+        crop_list = crops_many(meshes, K_orig, boxes, csize, colors=[annotations[kept[j]]['color'] for j in live], raster=shared, **ckw)
         for c, j in zip(crop_list, live):
             c.latent, c.intrinsics, c.extrinsics = refined[j]['latent'], K_orig, labels[j][2]
     kept = [i for i, lab in zip(kept, labels) if lab is not None]
@@ -175,12 +187,7 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
     label_type='maskrcnn' the matched detector masks are the label masks, so 'iou_mask' is filled.
     crops: refine_frame's (needs return_stages=True; the stages gain 'crops').  The windows are clipped to the sample's image and the RGB
     bytes come from the sample's image."""
-    if crops is not None and crops is not False and not return_stages:
-        raise ValueError("refine_sample: crops needs return_stages=True (the crops are returned among the stages)")
-    if verify is not None and verify is not False and not return_stages:
-        raise ValueError("refine_sample: verify needs return_stages=True (the verdicts are returned among the stages)")
-    if mesh_resolution is not None and not return_stages:
-        raise ValueError("refine_sample: mesh_resolution needs return_stages=True (the meshes are returned among the stages)")
+    mesh_resolution, verify, crops = _stage_options("refine_sample", return_stages, mesh_resolution, verify, crops)
     if label_type not in ('gt', 'rcnn', 'maskrcnn'):
         raise ValueError("refine_sample: label_type must be 'gt', 'rcnn' or 'maskrcnn'")
     device = grid.points.device
@@ -245,12 +252,12 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
                     nocs.append(uvw[j] / 255.)
                     latents.append(lat[j].to(precision))
     annotations = [{'bbox': lboxes[j], 'color': colors[j], 'depth': depths[j], 'nocs_pred': nocs[j]} for j in range(len(live))]
-    if verify is not None and verify is not False:
-        verify = dict({} if verify is True else verify, image_size=(W, H))
+    if verify is not None:
+        verify = dict(verify, image_size=(W, H))
         if masks is not None:
             verify.setdefault('label_masks', masks)
-    if crops is not None and crops is not False:
-        crops = dict({} if crops is True else crops, image_size=(W, H))
+    if crops is not None:
+        crops = dict(crops, image_size=(W, H))
     out = refine_frame(annotations, dsdf, grid, latents, K_orig, sample['world_to_cam'], iters, weights, pose_type=pose_type, scale=scale,
                        rendering_area=rendering_area, sampler=sampler, seed=seed, keys=None if keys is None else [keys[i] for i in live],
                        optimize_kwargs=optimize_kwargs, return_stages=return_stages, mesh_resolution=mesh_resolution, verify=verify, crops=crops)

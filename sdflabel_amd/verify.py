@@ -1,9 +1,11 @@
 """Verification of refined autolabels on the device (csrc/verify.hip; DESIGN.md "Verification").
 
-    from sdflabel_amd.verify import raster_many, band_counts, verify_many
+    from sdflabel_amd.verify import raster_many, raster_batch, band_counts, verify_many
 
 raster_many   camera-frame meshes -> mask, depth and winning triangle in each mesh's own window of the image, by an exact rasteriser whose
               result is defined independently of the schedule
+raster_batch  the same launches with the result kept packed (RasterBatch): what verify_many and export.crops_many read, and take as
+              `raster=` so that a frame is rendered once
 band_counts   lidar points taken to each annotation's lattice frame, the decoder there, and the integer counts of points in a band round
               the surface
 verify_many   both, the counts of the rendered mask against the 2-D label, ONE host read, and a verdict per annotation
@@ -43,9 +45,56 @@ def _intrinsics(K):
     return float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
 
 
-def _raster_packed(meshes, K, windows, image_size, z_min):
-    """the launches of raster_many: packed outputs and the device tables the count kernel takes"""
+class RasterBatch:
+    """A frame's meshes rendered into their windows, packed: what raster_batch made and what every stage that reads the rasters takes.
+    `.mask` uint8 [P], `.depth` float32 [P], `.triangle` int32 [P] and `.flags` int32 [B] are the rasteriser's packed outputs, `.vertices`
+    float32 [V][3] and `.faces` int32 [T][3] its packed inputs, `.d_voff`, `.d_toff`, `.d_poff` (int64 [B + 1]) and `.d_win` (int32 [4 B]) the
+    device tables; `.windows` int64 [B][4] and `.poff` int64 [B + 1] are their host copies.  `.P`, `.W`, `.H`, `.device` as passed to the
+    kernels.  `.k4` (four doubles), `.z_min` and `.sizes` (per mesh its vertex and face count) say what the batch was made with."""
+
+    def __init__(self, mask, depth, triangle, flags, vertices, faces, d_voff, d_toff, d_poff, d_win, windows, poff, P, W, H, device, k4, z_min, sizes):
+        self.mask, self.depth, self.triangle, self.flags, self.vertices, self.faces = mask, depth, triangle, flags, vertices, faces
+        self.d_voff, self.d_toff, self.d_poff, self.d_win, self.windows, self.poff = d_voff, d_toff, d_poff, d_win, windows, poff
+        self.P, self.W, self.H, self.device, self.k4, self.z_min, self.sizes = P, W, H, device, k4, z_min, sizes
+
+    def rasters(self):
+        """one Raster per mesh: views of the packed outputs"""
+        out = []
+        for b, (l, t, r, bt) in enumerate(self.windows.tolist()):
+            p0, p1 = int(self.poff[b]), int(self.poff[b + 1])
+            shape = (bt - t, r - l)
+            out.append(Raster(self.mask[p0:p1].view(shape), self.depth[p0:p1].view(shape), self.triangle[p0:p1].view(shape), (l, t, r, bt),
+                              self.flags[b]))
+        return out
+
+    def mask_counts(self, label=None):
+        """int32 [B][8] on the device: area, tight box l t r b, label area, intersection, flag"""
+        B = int(self.windows.shape[0])
+        out = torch.empty((B, 8), dtype=torch.int32, device=self.device)
+        if B:
+            with _lib.guard(self.device):
+                _lib.check(_lib.lib().sdfr_verify_mask_counts(_lib.ptr(self.mask) if self.P else None, _lib.ptr(label), _lib.ptr(self.d_win),
+                                                              _lib.ptr(self.d_poff), self.P, B, self.W, self.H, _lib.ptr(out), _lib.stream_ptr()),
+                           "sdfr_verify_mask_counts")
+        return out
+
+    def require(self, who, meshes, K, windows, image_size, z_min):
+        """refuse, on the host and before any launch, a batch that is not the one raster_batch(meshes, K, windows, image_size, z_min) makes"""
+        sizes = [(int(m.vertices.shape[0]), int(m.faces.shape[0])) for m in meshes]
+        made = (("meshes", self.sizes, sizes), ("image size", (self.W, self.H), (int(image_size[0]), int(image_size[1]))),
+                ("intrinsics", tuple(self.k4), _intrinsics(K)), ("z_min", self.z_min, float(z_min)),
+                ("windows", self.windows.tolist(), np.asarray(windows, dtype=np.int64).reshape(-1, 4).tolist()))
+        for what, has, wants in made:
+            if has != wants:
+                raise ValueError("%s: the raster batch was made for other %s (%s, not %s)" % (who, what, has, wants))
+        return self
+
+
+def raster_batch(meshes, K, windows, image_size, z_min=0.1):
+    """The launches of raster_many, kept packed: a RasterBatch, which verify_many and export.crops_many also take as `raster=` so that a
+    frame is rendered once.  Arguments as raster_many's."""
     L = _lib.lib()
+    meshes = list(meshes)
     W, H = int(image_size[0]), int(image_size[1])
     B = len(meshes)
     win = np.asarray(windows, dtype=np.int64).reshape(-1, 4)
@@ -60,8 +109,9 @@ def _raster_packed(meshes, K, windows, image_size, z_min):
         raise ValueError("verify: every window [l, t, r, b) must be clipped to the %d x %d image" % (W, H))
     k4 = (ctypes.c_double * 4)(*_intrinsics(K))
     dev = meshes[0].vertices.device if B else torch.device("cuda", torch.cuda.current_device())
-    voff = np.concatenate([[0], np.cumsum([int(m.vertices.shape[0]) for m in meshes])]).astype(np.int64)
-    toff = np.concatenate([[0], np.cumsum([int(m.faces.shape[0]) for m in meshes])]).astype(np.int64)
+    sizes = [(int(m.vertices.shape[0]), int(m.faces.shape[0])) for m in meshes]
+    voff = np.concatenate([[0], np.cumsum([v for v, _ in sizes])]).astype(np.int64)
+    toff = np.concatenate([[0], np.cumsum([t for _, t in sizes])]).astype(np.int64)
     poff = np.concatenate([[0], np.cumsum((win[:, 2] - win[:, 0]) * (win[:, 3] - win[:, 1]))]).astype(np.int64)
     V, T, P = int(voff[-1]), int(toff[-1]), int(poff[-1])
     table = _upload(torch.from_numpy(np.concatenate([voff, toff, poff, win.astype(np.int32).reshape(-1).view(np.int64) if B else
@@ -72,7 +122,7 @@ def _raster_packed(meshes, K, windows, image_size, z_min):
     verts = torch.cat([m.vertices.detach().float().reshape(-1, 3) for m in meshes]).contiguous() if B else torch.zeros((0, 3), device=dev)
     faces = torch.cat([m.faces.detach().to(torch.int32).reshape(-1, 3) for m in meshes]).contiguous() if B else \
         torch.zeros((0, 3), dtype=torch.int32, device=dev)
-    keys = torch.empty((P,), dtype=torch.int64, device=dev)
+    keys = torch.empty((P,), dtype=torch.int64, device=dev)                         # the rasteriser's workspace
     mask = torch.empty((P,), dtype=torch.uint8, device=dev)
     depth = torch.empty((P,), dtype=torch.float32, device=dev)
     tri = torch.empty((P,), dtype=torch.int32, device=dev)
@@ -83,18 +133,7 @@ def _raster_packed(meshes, K, windows, image_size, z_min):
             _lib.check(L.sdfr_mesh_raster(Pt(verts) if V else None, V, Pt(faces) if T else None, T, Pt(d_voff), Pt(d_toff), Pt(d_win), Pt(d_poff), P,
                                           B, W, H, k4, float(z_min), Pt(keys) if P else None, Pt(mask) if P else None, Pt(depth) if P else None,
                                           Pt(tri) if P else None, Pt(flags), _lib.stream_ptr()), "sdfr_mesh_raster")
-    return dict(mask=mask, depth=depth, triangle=tri, flags=flags, windows=win, poff=poff, d_win=d_win, d_poff=d_poff, P=P, W=W, H=H, device=dev,
-                vertices=verts, faces=faces, d_voff=d_voff, d_toff=d_toff, keys=keys)
-
-
-def _rasters(pk):
-    out = []
-    for b, (l, t, r, bt) in enumerate(pk["windows"].tolist()):
-        p0, p1 = int(pk["poff"][b]), int(pk["poff"][b + 1])
-        shape = (bt - t, r - l)
-        out.append(Raster(pk["mask"][p0:p1].view(shape), pk["depth"][p0:p1].view(shape), pk["triangle"][p0:p1].view(shape), (l, t, r, bt),
-                          pk["flags"][b]))
-    return out
+    return RasterBatch(mask, depth, tri, flags, verts, faces, d_voff, d_toff, d_poff, d_win, win, poff, P, W, H, dev, k4, float(z_min), sizes)
 
 
 @_lib.traced("raster_many")
@@ -108,19 +147,7 @@ def raster_many(meshes, K, windows, image_size, z_min=0.1):
     The result is defined (DESIGN.md "Verification"): float64 pinhole projection of the float32 vertices, pixel (x, y) sampled at the point
     (x, y), inclusive edges, both windings, perspective-correct depth, the nearest depth wins and on an exact tie the lowest triangle
     index.  The same bits on every run and in every batch.  Returns a list of Raster; no host synchronisation."""
-    return _rasters(_raster_packed(list(meshes), K, windows, image_size, z_min))
-
-
-def _mask_counts(pk, label=None):
-    """int32 [B][8] on the device: area, tight box l t r b, label area, intersection, flag"""
-    B = int(pk["windows"].shape[0])
-    out = torch.empty((B, 8), dtype=torch.int32, device=pk["device"])
-    if B:
-        with _lib.guard(pk["device"]):
-            _lib.check(_lib.lib().sdfr_verify_mask_counts(_lib.ptr(pk["mask"]) if pk["P"] else None, _lib.ptr(label), _lib.ptr(pk["d_win"]),
-                                                          _lib.ptr(pk["d_poff"]), pk["P"], B, pk["W"], pk["H"], _lib.ptr(out), _lib.stream_ptr()),
-                       "sdfr_verify_mask_counts")
-    return out
+    return raster_batch(meshes, K, windows, image_size, z_min).rasters()
 
 
 def _pose_rows(params_list, device):
@@ -202,8 +229,8 @@ def band_counts(dsdf, params_list, clouds, band=0.2, staging_bytes=STAGING_BYTES
     units of the cloud, metres for KITTI).  Points outside the cube are out of the band whatever the decoder says there.
     Returns int32 [B][3] on the device: n_pts, n_cube, n_band.  No host synchronisation.  With return_details also a dict of the rows, the
     decoder's values, the in-cube bytes, the pose rows and the point offsets."""
-    pk = _band_packed(dsdf, list(params_list), list(clouds), band, staging_bytes, keep_rows=return_details)
-    return (pk["counts"], pk) if return_details else pk["counts"]
+    d = _band_packed(dsdf, list(params_list), list(clouds), band, staging_bytes, keep_rows=return_details)
+    return (d["counts"], d) if return_details else d["counts"]
 
 
 def label_windows(boxes, image_size, margin=0.25):
@@ -257,13 +284,15 @@ def _pack_labels(label_masks, box, win, poff, dev):
 
 @_lib.traced("verify_many")
 def verify_many(dsdf, params_list, meshes, clouds, K, boxes, image_size, label_masks=None, margin=0.25, band=0.2, min_iou=0.7, min_share=0.6,
-                iou='box', z_min=0.1, staging_bytes=STAGING_BYTES):
+                iou='box', z_min=0.1, staging_bytes=STAGING_BYTES, raster=None):
     """The two tests of an autolabel, for all annotations of a frame.
 
     params_list, clouds: band_counts'.  meshes: the refined shapes as camera-frame Mesh objects.  K, image_size: the camera's intrinsics
     (host) and (W, H).  boxes: the 2-D labels [l, t, r, b]; each is taken outward to a half-open integer box, and the mesh is rendered into
     that box grown by `margin` of its width / height on every side and clipped to the image (label_windows).  label_masks: per annotation
     a 2-D uint8 / bool label mask of the window's shape -- or of the label box's shape, which is placed into the window -- or None.
+    raster: the RasterBatch of these meshes in these windows (raster_batch(meshes, K, label_windows(boxes, image_size, margin)[1],
+    image_size, z_min)), to be read instead of rendering again; one made with anything else is refused with a ValueError.
 
     ONE host read, of all the counts.  Returns per annotation a dict:
       iou_box    IoU of the tight box of the rendered mask and the label box, both half-open integer boxes, float64 on the host
@@ -289,11 +318,11 @@ def verify_many(dsdf, params_list, meshes, clouds, K, boxes, image_size, label_m
     if B == 0:
         return []
     box, win = label_windows(boxes, image_size, margin)
-    pk = _raster_packed(meshes, K, win, image_size, z_min)
-    label = None if label_masks is None else _pack_labels(label_masks, box, win, pk["poff"], pk["device"])
-    c8 = _mask_counts(pk, label)
+    rb = raster_batch(meshes, K, win, image_size, z_min) if raster is None else raster.require("verify_many", meshes, K, win, image_size, z_min)
+    label = None if label_masks is None else _pack_labels(label_masks, box, win, rb.poff, rb.device)
+    c8 = rb.mask_counts(label)
     c3 = band_counts(dsdf, params_list, clouds, band=band, staging_bytes=staging_bytes)
-    host = torch.cat([c8, c3.to(c8.device), pk["flags"][:, None]], 1).cpu().numpy().astype(np.int64)          # the one host read
+    host = torch.cat([c8, c3.to(c8.device), rb.flags[:, None]], 1).cpu().numpy().astype(np.int64)          # the one host read
     out = []
     for b in range(B):
         area, mbox, la, inter, bad = int(host[b, 0]), [int(x) for x in host[b, 1:5]], int(host[b, 5]), int(host[b, 6]), int(host[b, 7])

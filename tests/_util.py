@@ -32,6 +32,23 @@ def build_c_abi_smoke(out_dir):
     return exe
 
 
+def build_host_program(out_dir, source, name, extra=()):
+    """Compile a host harness of one of csrc's headers (`source`, relative to tests/) into out_dir/name with the flags the headers are
+    written for; `extra` adds flags (the sanitizer builds).  Skips the test without a host C++ compiler.  Returns the binary path."""
+    import shutil
+    import subprocess
+    import pytest
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = os.path.join(str(out_dir), name)
+    r = subprocess.run([cxx, "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"] + list(extra) +
+                       ["-I" + os.path.join(ROOT, "sdflabel_amd", "csrc"), os.path.join(ROOT, "tests", source), "-o", exe],
+                      capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return exe
+
+
 def pattern_weights(shape, salt):
     """Deterministic pseudo-random weights in [-1, 1] (integer hash of the flat index: exact in float32 on every platform); the same
     function as tools/make_golden.py's, so that the gradient functionals of the large goldens (G10) need no stored weight arrays."""

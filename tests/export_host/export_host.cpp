@@ -45,11 +45,10 @@ int main(int argc, char** argv) {
     for (int b = 0; b < B; ++b) {
         const int32_t* w = &windows[4 * b];
         const int32_t* x = &boxes[4 * b];
-        if (!(0 <= w[0] && w[0] <= w[2] && w[2] <= W && 0 <= w[1] && w[1] <= w[3] && w[3] <= H)) return 3;
         if (!(x[0] <= x[2] && x[1] <= x[3])) return 3;                   // (a box outside its window is a case: the flag is expected)
-        if (voff[b + 1] < voff[b] || toff[b + 1] < toff[b]) return 3;
         poff[b + 1] = poff[b] + (int64_t)(w[2] - w[0]) * (w[3] - w[1]);
         qoff[b + 1] = qoff[b] + (int64_t)(x[2] - x[0]) * (x[3] - x[1]);
+        if (voff[b + 1] < voff[b] || toff[b + 1] < toff[b] || poff[b + 1] < poff[b]) return 3;
     }
     const int64_t P = poff[B], Q = qoff[B];
     if (!rd(f, vertices, 3 * (size_t)V) || !rd(f, attributes, 3 * (size_t)V) || !rd(f, faces, 3 * (size_t)T)) return 3;
@@ -62,16 +61,16 @@ int main(int argc, char** argv) {
         const int b = verify_owner(toff.data(), B, g);
         const int64_t v0 = voff[b], nv = voff[b + 1] - v0;
         const int32_t* w = &windows[4 * b];
-        const int32_t i0 = faces[3 * g], i1 = faces[3 * g + 1], i2 = faces[3 * g + 2];
-        if (!(i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < nv && i1 < nv && i2 < nv)) continue;
+        const int32_t* fc = &faces[3 * g];
+        if (!verify_face_ok(fc, nv) || !verify_window_ok(w, &poff[b], P, W, H)) continue;
         VerifyTri tri;
-        if (verify_tri_setup(&vertices[3 * (v0 + i0)], &vertices[3 * (v0 + i1)], &vertices[3 * (v0 + i2)], K, z_min, w[0], w[1], w[2], w[3], &tri) !=
-            VERIFY_TRI_OK)
+        if (verify_tri_setup(&vertices[3 * (v0 + fc[0])], &vertices[3 * (v0 + fc[1])], &vertices[3 * (v0 + fc[2])], K, z_min, w[0], w[1], w[2], w[3],
+                             &tri) != VERIFY_TRI_OK)
             continue;
         for (int y = tri.y0; y <= tri.y1; ++y)
             for (int x = tri.x0; x <= tri.x1; ++x) {
                 const uint64_t key = verify_pixel_key(&tri, x, y, (uint32_t)(g - toff[b]));
-                const int64_t at = poff[b] + (int64_t)(y - w[1]) * (w[2] - w[0]) + (x - w[0]);
+                const int64_t at = verify_window_pixel(w, poff[b], x, y);
                 if (key < keys[at]) keys[at] = key;
             }
     }
@@ -87,7 +86,7 @@ int main(int argc, char** argv) {
         for (int64_t i = 0; i < P; ++i) {
             const int b = verify_owner(poff.data(), B, i);
             const int32_t* w = &windows[4 * b];
-            if (!crop_window_ok(w, &poff[b], P, W, H) || i < poff[b] || i >= poff[b + 1]) {
+            if (!verify_window_ok(w, &poff[b], P, W, H) || i < poff[b] || i >= poff[b + 1]) {
                 owner[i] = -1;
                 continue;
             }
@@ -98,8 +97,8 @@ int main(int argc, char** argv) {
         }
     }
     // export: init, per box pixel, scrub
-    CropArgs a = {vertices.data(), faces.data(), attributes.data(), voff.data(), toff.data(), windows.data(), poff.data(), boxes.data(), qoff.data(),
-                  B, W, H, V, T, P, Q, {K[0], K[1], K[2], K[3]}, z_min};
+    const CropArgs a = {raster_args(vertices.data(), V, faces.data(), T, voff.data(), toff.data(), windows.data(), poff.data(), P, B, W, H, K, z_min),
+                        attributes.data(), boxes.data(), qoff.data(), Q};
     std::vector<int32_t> flags(B, 0);
     for (int b = 0; b < B; ++b) flags[b] = crop_anno_ok(&a, b) ? 0 : VERIFY_FLAG_INVALID;
     std::vector<uint8_t> uvw(3 * (size_t)Q), rgb(has_colors ? 3 * (size_t)Q : 0);
@@ -123,14 +122,14 @@ int main(int argc, char** argv) {
         const int32_t* w = &windows[4 * b];
         const int32_t* box = &boxes[4 * b];
         int32_t* o = &counts[CROP_COUNTS * b];
-        const bool fits = crop_window_ok(w, &poff[b], P, W, H) && crop_box_ok(box, w, &qoff[b], Q);
+        const bool fits = verify_window_ok(w, &poff[b], P, W, H) && crop_box_ok(box, w, &qoff[b], Q);
         const int32_t word = flags[b] | (fits ? 0 : VERIFY_FLAG_INVALID);
         o[3] = word;
         if (word & VERIFY_FLAG_INVALID) continue;
-        const int bw = box[2] - box[0], ww = w[2] - w[0], n = bw * (box[3] - box[1]);
+        const int bw = box[2] - box[0], n = bw * (box[3] - box[1]);
         for (int i = 0; i < n; ++i) {
             const int x = box[0] + i % bw, y = box[1] + i / bw;
-            const int64_t at = poff[b] + (int64_t)(y - w[1]) * ww + (x - w[0]);
+            const int64_t at = verify_window_pixel(w, poff[b], x, y);
             const bool c = mask[at] != 0;
             o[1] += c;
             o[2] += c && (!occlusion || owner[at] == b);

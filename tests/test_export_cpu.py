@@ -6,7 +6,6 @@ library on the new exports."""
 import json
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -16,6 +15,7 @@ from tests import _export_cases as EC
 from tests import _export_ref as ER
 from tests import _verify_cases as VC
 from tests import _verify_ref as VR
+from tests._util import build_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -193,21 +193,9 @@ def test_rgb_bytes():
 
 # ---- the header on the host --------------------------------------------------------------------------------------------------------------------
 
-def _build(tmp, name, extra):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp / name)
-    r = subprocess.run([cxx, "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"] + extra +
-                       ["-I" + os.path.join(ROOT, "sdflabel_amd", "csrc"), os.path.join(ROOT, "tests", "export_host", "export_host.cpp"), "-o", exe],
-                      capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    return _build(tmp_path_factory.mktemp("export_host"), "export_host", [])
+    return build_host_program(tmp_path_factory.mktemp("export_host"), "export_host/export_host.cpp", "export_host")
 
 
 def run_host(exe, b, tmp):
@@ -268,10 +256,16 @@ def test_header_on_the_host_reproduces_the_restatement(host_program, tmp_path, b
 
 def test_header_on_the_host_under_the_sanitizers(tmp_path, batches, refs):
     """exact-size buffers: an index outside a window, a box, a mesh or a colour crop is an error here"""
-    exe = _build(tmp_path, "export_host_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    exe = build_host_program(tmp_path, "export_host/export_host.cpp", "export_host_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    ran = {}
     for name, b in batches.items():
         out, areas = run_host(exe, b, str(tmp_path))
         check_host(out, areas, refs[name], name)
+        ran[name] = out[3].tolist()
+    # the cases in which only the predicates the kernels share keep the reads inside the buffers: triangle indices 7 and -3 for a mesh of one
+    # triangle, a box that leaves its window (its offsets then fit no window pixel), an empty window, a mesh without triangles
+    assert ran["bad_triangle_index"] == [ER.FLAG_INVALID, 0] and ran["box_outside_window"] == [ER.FLAG_INVALID, 0]
+    assert ran["empty_window"] == [0] and ran["empty_mesh"] == [0]
 
 
 # ---- the writer ------------------------------------------------------------------------------------------------------------------------------------

@@ -285,6 +285,76 @@ def test_two_runs_give_the_same_bits(batches):
     assert sum(int(x.counts[2]) for x in a) > 1000
 
 
+def same_crops(got, want):
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g.box == w.box and g.window == w.window and g.uvw.shape == w.uvw.shape
+        assert torch.equal(g.uvw, w.uvw) and torch.equal(g.counts, w.counts) and torch.equal(g.flags, w.flags)
+        assert (g.rgb is None and w.rgb is None) or torch.equal(g.rgb, w.rgb)
+
+
+def test_crops_many_with_a_raster_batch_gives_the_same_bits(batches):
+    """raster= skips the rasterisation and nothing else; the third annotation's window is cut by the image border"""
+    meshes, attrs, labels, colors = frame_problem(batches)
+    dm, da = on_device(meshes, attrs)
+    size = (VC.W, VC.H)
+    rb = V.raster_batch(dm, VC.K8, V.label_windows(labels, size, 0.25)[1], size)
+    for occ in (True, False):
+        want = E.crops_many(dm, VC.K8, labels, size, colors=colors, attributes=da, occlusion=occ)
+        syncs, got = count_syncs(lambda: E.crops_many(dm, VC.K8, labels, size, colors=colors, attributes=da, occlusion=occ, raster=rb))
+        assert syncs == 0, syncs
+        same_crops(got, want)
+        print("occlusion %s: visible %s" % (occ, [int(c.counts[2]) for c in got]))
+        assert want[2].box == (0, 0, 30, 40) and want[2].window[:2] == (0, 0) and sum(int(c.counts[2]) for c in want) > 1000
+    # an empty window and a mesh without triangles beside a usual annotation
+    empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+    meshes, attrs = [meshes[0], empty, meshes[1]], [attrs[0], np.zeros((0, 3), np.float32), attrs[1]]
+    labels = [[10, 10, 10, 20], labels[0], labels[1]]
+    rng = np.random.default_rng(22)
+    colors = [EC.colour_crop(rng, (10, 10, 10, 20)), colors[0], colors[1]]
+    dm, da = on_device(meshes, attrs)
+    rb = V.raster_batch(dm, VC.K8, V.label_windows(labels, size, 0.25)[1], size)
+    want = E.crops_many(dm, VC.K8, labels, size, colors=colors, attributes=da)
+    same_crops(E.crops_many(dm, VC.K8, labels, size, colors=colors, attributes=da, raster=rb), want)
+    assert want[0].uvw.shape == (10, 0, 3) and want[0].window[0] == want[0].window[2] and int(want[1].counts[1]) == 0 and int(want[2].counts[2]) > 0
+    assert [int(c.flags) for c in want] == [0, 0, 0]
+
+
+def test_a_raster_batch_made_for_something_else_is_refused(batches, monkeypatch):
+    """the host check of raster= comes before any launch: the library is not even looked up"""
+    meshes, attrs, labels, colors = frame_problem(batches)
+    dm, da = on_device(meshes, attrs)
+    size, K = (VC.W, VC.H), VC.K8
+    win = V.label_windows(labels, size, 0.25)[1]
+    other_faces = cam_mesh(meshes[2][0], np.concatenate([meshes[2][1], meshes[2][1]]))
+    assert len(other_faces.vertices) == len(dm[2].vertices) and len(other_faces.faces) != len(dm[2].faces)
+    K_ulp = tuple(np.nextafter(k, np.inf) if i == 2 else k for i, k in enumerate(K))
+    stale = {
+        "margin": V.raster_batch(dm, K, win, size),
+        "one mesh fewer": V.raster_batch(dm[:2], K, win[:2], size),
+        "face count": V.raster_batch(dm[:2] + [other_faces], K, win, size),
+        "z_min": V.raster_batch(dm, K, win, size, z_min=0.2),
+        "image_size": V.raster_batch(dm, K, win, (VC.W + 1, VC.H)),
+        "K one ulp": V.raster_batch(dm, K_ulp, win, size),
+    }
+    good = V.raster_batch(dm, K, win, size)
+    torch.cuda.synchronize()
+
+    def no_library():
+        raise AssertionError("the library was reached before the raster batch was refused")
+
+    monkeypatch.setattr(_lib, "lib", no_library)
+    for name, rb in stale.items():
+        with pytest.raises(ValueError) as e:
+            E.crops_many(dm, K, labels, size, colors=colors, attributes=da, margin=0.1 if name == "margin" else 0.25, raster=rb)
+        print("%s: %s" % (name, str(e.value)[:160]))
+        assert "raster batch" in str(e.value), name
+    with pytest.raises(ValueError):
+        V.verify_many(None, [None] * 3, dm, [None] * 3, K, labels, size, margin=0.1, raster=good)
+    with pytest.raises(AssertionError):                                                       # and a batch that fits gets as far as the library
+        E.crops_many(dm, K, labels, size, colors=colors, attributes=da, raster=good)
+
+
 # ---- the frame pipeline --------------------------------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
@@ -312,7 +382,8 @@ def frame_export(tmp_path_factory):
     path = tmp_path_factory.mktemp("crops")
     with E.CropWriter(path) as writer:
         syncs, written = count_syncs(lambda: export_frame(st, writer, only_ok=False))
-    return dict(est0=est0, kept0=kept0, est=est, kept=kept, stages=st, K=K_orig, path=str(path), written=written, syncs=syncs, annos=annos)
+    return dict(est0=est0, kept0=kept0, est=est, kept=kept, stages=st, K=K_orig, path=str(path), written=written, syncs=syncs, annos=annos,
+                args=args, dec16=dec16)
 
 
 def test_refine_frame_crops(frame_export):
@@ -376,6 +447,35 @@ def test_refine_frame_crops(frame_export):
     assert export_frame(st, Sink(), only_ok=False, min_visible=1.1) == []
     with pytest.raises(ValueError):
         export_frame({k: v for k, v in st.items() if k != "verify"}, Sink())
+
+
+def test_refine_frame_rasterises_once(frame_export, monkeypatch):
+    """verify and crops that agree on image size, margin and z_min share one raster batch; otherwise each makes its own.  Either way the
+    stages are those of separate verify_many / crops_many calls on stages['meshes']"""
+    from sdflabel_amd.pipelines import optimizer as OP
+    from sdflabel_amd.pipelines.frame import _grown_size, refine_frame
+    f = frame_export
+    calls = []
+    real = V.raster_batch
+    monkeypatch.setattr(V, "raster_batch", lambda *a, **k: calls.append(1) or real(*a, **k))
+    for verify, crops, n in ((True, True, 1), ({"margin": 0.25}, {"margin": 0.5}, 2)):
+        OP.clear_refiner_cache()
+        del calls[:]
+        est, kept, st = refine_frame(*f["args"], seed=7, return_stages=True, mesh_resolution=16, verify=verify, crops=crops)
+        print("verify=%s crops=%s: %d raster batches" % (verify, crops, len(calls)))
+        assert len(calls) == n
+        assert kept == f["kept0"]
+        live = [j for j, lab in enumerate(st["labels"]) if lab is not None]
+        boxes = [f["annos"][i]["bbox"] for i in kept]
+        vm, cm = (0.25, 0.25) if verify is True else (verify["margin"], crops["margin"])
+        want_v = V.verify_many(f["dec16"], [st["params"][j] for j in live], st["meshes"], [st["lidar"][i][0] for i in kept], f["K"], boxes,
+                               _grown_size(boxes, vm), margin=vm)
+        want_c = E.crops_many(st["meshes"], f["K"], boxes, _grown_size(boxes, cm), colors=[f["annos"][i]["color"] for i in kept], margin=cm)
+        assert st["verify"] == want_v
+        same_crops(st["crops"], want_c)
+        if verify is True:                                                                     # and the fixture's own call gave these bits
+            assert st["verify"] == f["stages"]["verify"]
+            same_crops(st["crops"], f["stages"]["crops"])
 
 
 def test_exported_folder_feeds_a_training_step(frame_export):

@@ -178,11 +178,11 @@ def test_mask_counts_equal_numpy(cases, refs):
     names = ["edges_through_samples", "near_over_far", "partly_outside_window", "empty_mesh", "empty_window", "full_window"]
     meshes = [cam_mesh(cases[n][0], cases[n][1]) for n in names]
     wins = np.asarray([cases[n][3] for n in names])
-    pk = V._raster_packed(meshes, VC.K8, wins, (VC.W, VC.H), 0.1)
+    rb = V.raster_batch(meshes, VC.K8, wins, (VC.W, VC.H), 0.1)
     rng = np.random.default_rng(9)
     labels = [(rng.random(refs[n][0].shape) < 0.4).astype(np.uint8) for n in names]
     packed = torch.from_numpy(np.concatenate([l.reshape(-1) for l in labels])).to(DEV)
-    plain, with_label = V._mask_counts(pk).cpu().numpy(), V._mask_counts(pk, packed).cpu().numpy()
+    plain, with_label = rb.mask_counts().cpu().numpy(), rb.mask_counts(packed).cpu().numpy()
     for b, n in enumerate(names):
         print(n, plain[b].tolist(), with_label[b].tolist())
         assert plain[b].tolist() == VR.mask_counts(refs[n][0], wins[b]).tolist(), n
@@ -326,6 +326,23 @@ def test_verify_many_accepts_the_shape_and_rejects_it_moved(ell):
     assert not none["ok"] and "no_points" in none["why"] and none["share"] == 0.0
     with pytest.raises(ValueError):
         V.verify_many(dec, [PARAMS], [cam], [cam.vertices], K_ELL, [box], (VC.W, VC.H), iou="mask")
+
+
+def test_verify_many_with_a_raster_batch_gives_the_same_verdicts(ell):
+    """raster= skips the rasterisation and nothing else: equal dicts, still one host read; also with an empty window and an empty mesh"""
+    dec, m, cam = ell
+    box = projected_box(cam)
+    none = cam_mesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+    meshes, boxes = [cam, cam, none], [box, [10, 10, 10, 20], box]
+    lab = [None, None, torch.ones((box[3] - box[1], box[2] - box[0]), dtype=torch.uint8, device=DEV)]
+    args = ([PARAMS] * 3, meshes, [cam.vertices] * 3, K_ELL, boxes, (VC.W, VC.H))
+    want = V.verify_many(dec, *args, label_masks=lab)
+    rb = V.raster_batch(meshes, K_ELL, V.label_windows(boxes, (VC.W, VC.H), 0.25)[1], (VC.W, VC.H))
+    syncs, got = count_syncs(lambda: V.verify_many(dec, *args, label_masks=lab, raster=rb))
+    print(got)
+    assert syncs == 1, syncs
+    assert got == want
+    assert got[0]["ok"] and got[1]["window"][0] == got[1]["window"][2] and got[1]["area"] == 0 and got[2]["area"] == 0 and got[2]["flags"] == 0
 
 
 # ---- the frame pipeline --------------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,6 @@
 """Mesh extraction without a GPU: the invariants of the numpy restatement (tests/_mesh_ref.py), the per-point header csrc/mesh_cells.h
 compiled for the host and compared with the restatement bit for bit, and the host side of sdflabel_amd.mesh (files, camera frame)."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -9,6 +8,7 @@ import pytest
 import torch
 
 from tests import _mesh_ref as MR
+from tests._util import build_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPHERE_VOLUME = 4.0 / 3.0 * np.pi * 0.6 ** 3
@@ -62,14 +62,7 @@ def test_sphere_volume_converges_monotonically():
 
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("mesh_host") / "mesh_host")
-    r = subprocess.run([cxx, "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sdflabel_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "mesh_host", "mesh_host.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return build_host_program(tmp_path_factory.mktemp("mesh_host"), "mesh_host/mesh_host.cpp", "mesh_host")
 
 
 def run_host(exe, sdf, tmp):

@@ -3,7 +3,6 @@ compiled for the host and compared with the restatement bit for bit (once more u
 the agreement of header, ctypes table and library on the new exports."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -11,6 +10,7 @@ import pytest
 
 from tests import _verify_cases as VC
 from tests import _verify_ref as VR
+from tests._util import build_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -113,21 +113,9 @@ def test_mask_counts_and_point_frame_of_the_restatement(refs, cases):
 
 # ---- the header on the host --------------------------------------------------------------------------------------------------------------------
 
-def _build(tmp, name, extra):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp / name)
-    r = subprocess.run([cxx, "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"] + extra +
-                       ["-I" + os.path.join(ROOT, "sdflabel_amd", "csrc"), os.path.join(ROOT, "tests", "verify_host", "verify_host.cpp"), "-o", exe],
-                      capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    return _build(tmp_path_factory.mktemp("verify_host"), "verify_host", [])
+    return build_host_program(tmp_path_factory.mktemp("verify_host"), "verify_host/verify_host.cpp", "verify_host")
 
 
 def run_host(exe, names, cases, K, pp, tmp):
@@ -192,11 +180,22 @@ def test_header_on_the_host_reproduces_the_restatement(host_program, tmp_path, c
 
 def test_header_on_the_host_under_the_sanitizers(tmp_path, cases, refs):
     """exact-size buffers: an index outside a window, a mesh or a cloud is an error here"""
-    exe = _build(tmp_path, "verify_host_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    exe = build_host_program(tmp_path, "verify_host/verify_host.cpp", "verify_host_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
     pp = VC.point_problem()
     names = k8_names(cases)
     out, wins = run_host(exe, names, cases, VC.K8, pp, str(tmp_path))
     check_host(out, wins, names, refs, pp)
+    # the cases in which only the predicates the kernels share (verify_face_ok, verify_window_ok) keep the reads inside the buffers
+    flags = dict(zip(names, out[3].tolist()))
+    assert flags["bad_index"] == VR.FLAG_INVALID and flags["behind_z_min"] == VR.FLAG_BEHIND and flags["empty_mesh"] == flags["empty_window"] == 0
+    v, f = cases["edges_through_samples"][:2]
+    broken = dict(cases, window_outside_image=(v, f, VC.K8, (60, 40, 70, 50), 0.1))
+    names = ["edges_through_samples", "window_outside_image", "bad_index"]
+    (mask, _, tri, flags, counts, _, _, _), wins = run_host(exe, names, broken, VC.K8, pp, str(tmp_path))
+    n0 = refs["edges_through_samples"][0].size
+    assert mask[:n0].tobytes() == refs["edges_through_samples"][0].tobytes() and mask[n0 + 100:].tobytes() == refs["bad_index"][0].tobytes()
+    assert not mask[n0:n0 + 100].any() and (tri[n0:n0 + 100] == -1).all()
+    assert flags.tolist() == [0, VR.FLAG_INVALID, VR.FLAG_INVALID] and counts[8:16].tolist() == [0] * 7 + [VR.FLAG_INVALID]
 
 
 # ---- header, ctypes table, library -------------------------------------------------------------------------------------------------------------

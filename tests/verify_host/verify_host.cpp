@@ -47,9 +47,8 @@ int main(int argc, char** argv) {
     std::vector<int64_t> poff(B + 1, 0);
     for (int b = 0; b < B; ++b) {
         const int32_t* w = &windows[4 * b];
-        if (!(0 <= w[0] && w[0] <= w[2] && w[2] <= W && 0 <= w[1] && w[1] <= w[3] && w[3] <= H)) return 3;
-        if (voff[b + 1] < voff[b] || toff[b + 1] < toff[b]) return 3;
         poff[b + 1] = poff[b] + (int64_t)(w[2] - w[0]) * (w[3] - w[1]);
+        if (voff[b + 1] < voff[b] || toff[b + 1] < toff[b] || poff[b + 1] < poff[b]) return 3;
     }
     const int64_t P = poff[B];
     // raster: keys by a sequential minimum
@@ -59,20 +58,20 @@ int main(int argc, char** argv) {
         const int b = verify_owner(toff.data(), B, g);
         const int64_t v0 = voff[b], nv = voff[b + 1] - v0;
         const int32_t* w = &windows[4 * b];
-        const int32_t i0 = faces[3 * g], i1 = faces[3 * g + 1], i2 = faces[3 * g + 2];
-        if (!(i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < nv && i1 < nv && i2 < nv)) {
+        const int32_t* fc = &faces[3 * g];
+        if (!verify_face_ok(fc, nv) || !verify_window_ok(w, &poff[b], P, W, H)) {       // as verify_load_tri of verify.hip
             flags[b] |= VERIFY_FLAG_INVALID;
             continue;
         }
         VerifyTri tri;
-        const int st = verify_tri_setup(&vertices[3 * (v0 + i0)], &vertices[3 * (v0 + i1)], &vertices[3 * (v0 + i2)], K, zb[0], w[0], w[1], w[2],
-                                        w[3], &tri);
+        const int st = verify_tri_setup(&vertices[3 * (v0 + fc[0])], &vertices[3 * (v0 + fc[1])], &vertices[3 * (v0 + fc[2])], K, zb[0], w[0], w[1],
+                                        w[2], w[3], &tri);
         if (st == VERIFY_TRI_BEHIND) flags[b] |= VERIFY_FLAG_BEHIND;
         if (st != VERIFY_TRI_OK) continue;
         for (int y = tri.y0; y <= tri.y1; ++y)
             for (int x = tri.x0; x <= tri.x1; ++x) {
                 const uint64_t key = verify_pixel_key(&tri, x, y, (uint32_t)(g - toff[b]));
-                const int64_t at = poff[b] + (int64_t)(y - w[1]) * (w[2] - w[0]) + (x - w[0]);
+                const int64_t at = verify_window_pixel(w, poff[b], x, y);
                 if (key < keys[at]) keys[at] = key;
             }
     }
@@ -84,6 +83,11 @@ int main(int argc, char** argv) {
     std::vector<int32_t> counts(8 * (size_t)B, 0);
     for (int b = 0; b < B; ++b) {
         const int32_t* w = &windows[4 * b];
+        int32_t* o = &counts[8 * b];
+        if (!verify_window_ok(w, &poff[b], P, W, H)) {
+            o[7] = VERIFY_FLAG_INVALID;
+            continue;
+        }
         const int ww = w[2] - w[0], n = ww * (w[3] - w[1]);
         int area = 0, x0 = INT32_MAX, y0 = INT32_MAX, x1 = -1, y1 = -1;
         for (int i = 0; i < n; ++i)
@@ -92,7 +96,6 @@ int main(int argc, char** argv) {
                 ++area;
                 x0 = x < x0 ? x : x0, x1 = x > x1 ? x : x1, y0 = y < y0 ? y : y0, y1 = y > y1 ? y : y1;
             }
-        int32_t* o = &counts[8 * b];
         o[0] = area;
         if (area) o[1] = x0, o[2] = y0, o[3] = x1 + 1, o[4] = y1 + 1;
     }

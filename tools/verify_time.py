@@ -97,20 +97,21 @@ def main():
             clouds.append(m.vertices[torch.from_numpy(rng.choice(len(v), NPTS, replace=len(v) < NPTS)).to(DEV)].contiguous())
         size = (W, H)
         _, win = V.label_windows(boxes, size)
-        pk = V._raster_packed(meshes, K, win, size, 0.1)
+        rb = V.raster_batch(meshes, K, win, size, 0.1)
+        keys = torch.empty((rb.P,), dtype=torch.int64, device=DEV)
         _, d = V.band_counts(dec, params, clouds, return_details=True)
         k4 = (ctypes.c_double * 4)(F, F, K[0, 2], K[1, 2])
         st = _lib.stream_ptr()
-        Vn, Tn, N = int(pk["vertices"].shape[0]), int(pk["faces"].shape[0]), int(d["points"].shape[0])
+        Vn, Tn, N = int(rb.vertices.shape[0]), int(rb.faces.shape[0]), int(d["points"].shape[0])
         Ld = int(d["latents"].shape[1])
         counts8 = torch.empty((B, 8), dtype=torch.int32, device=DEV)
         counts3 = torch.empty((B, 3), dtype=torch.int32, device=DEV)
         stage = {
             "raster": event_ms(lambda: _lib.check(L.sdfr_mesh_raster(
-                P(pk["vertices"]), Vn, P(pk["faces"]), Tn, P(pk["d_voff"]), P(pk["d_toff"]), P(pk["d_win"]), P(pk["d_poff"]), pk["P"], B, W, H, k4, 0.1,
-                P(pk["keys"]), P(pk["mask"]), P(pk["depth"]), P(pk["triangle"]), P(pk["flags"]), st), "sdfr_mesh_raster")),
+                P(rb.vertices), Vn, P(rb.faces), Tn, P(rb.d_voff), P(rb.d_toff), P(rb.d_win), P(rb.d_poff), rb.P, B, W, H, k4, 0.1,
+                P(keys), P(rb.mask), P(rb.depth), P(rb.triangle), P(rb.flags), st), "sdfr_mesh_raster")),
             "mask_counts": event_ms(lambda: _lib.check(L.sdfr_verify_mask_counts(
-                P(pk["mask"]), None, P(pk["d_win"]), P(pk["d_poff"]), pk["P"], B, W, H, P(counts8), st), "sdfr_verify_mask_counts")),
+                P(rb.mask), None, P(rb.d_win), P(rb.d_poff), rb.P, B, W, H, P(counts8), st), "sdfr_verify_mask_counts")),
             "point_rows": event_ms(lambda: _lib.check(L.sdfr_verify_point_rows(
                 P(d["points"]), N, P(d["d_ptoff"]), B, P(d["pose"]), P(d["latents"]), Ld, 0, N, P(d["rows"]), P(d["in_cube"]), st),
                 "sdfr_verify_point_rows")),
@@ -124,7 +125,7 @@ def main():
         entry = {"stage_ms": {a: round(b, 4) for a, b in stage.items()},
                  "verify_many_ms": round(host_ms(call), 4),
                  "meshes_many_R64_ms": round(host_ms(lambda: M.meshes_many(dec, params, resolution=64)), 4),
-                 "triangles": Tn, "window_pixels": pk["P"], "points": N, "kernel_launches": kl, "copies": cp,
+                 "triangles": Tn, "window_pixels": rb.P, "points": N, "kernel_launches": kl, "copies": cp,
                  "host_synchronisations": count_syncs(call), "accepted": sum(r["ok"] for r in verdicts),
                  "iou_box": [round(r["iou_box"], 4) for r in verdicts], "share": [round(r["share"], 4) for r in verdicts]}
         if B == 1:
@@ -138,7 +139,7 @@ def main():
             c3 = VR.band_counts(sdf, inside, d["ptoff"], pose, 0.2)
             t2 = time.perf_counter()
             entry["numpy_restatement_ms"] = {"raster": round((t1 - t0) * 1e3, 1), "counts_rows_band": round((t2 - t1) * 1e3, 3)}
-            entry["numpy_agrees"] = bool(rm[0].tobytes() == pk["mask"].cpu().numpy().tobytes() and c8[0] == verdicts[0]["area"]
+            entry["numpy_agrees"] = bool(rm[0].tobytes() == rb.mask.cpu().numpy().tobytes() and c8[0] == verdicts[0]["area"]
                                          and c3[0].tolist() == [verdicts[0]["n_pts"], verdicts[0]["n_cube"], verdicts[0]["n_band"]])
         res["cases"]["B%d" % B] = entry
         print("B=%d" % B, json.dumps(entry), flush=True)
