@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 413        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 414        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -44,7 +44,8 @@ extern "C" {
  * sdfr_css_latent; 407: its training losses and gradients, sdfr_css_head_loss and sdfr_css_latent_loss; 408: the road-plane removal, sdfr_lidar_normals_ws_bytes,
  * sdfr_lidar_normals and sdfr_depth_map_masked; 409: the training-crop augmentation, sdfr_augment; 410: the grid forward with the caller's tile order,
  * sdfr_grid_tile_order and sdfr_mlp_forward_ordered; 411: triangle meshes, sdfr_mesh_*; 412: verification of
- * refined labels, sdfr_mesh_raster and sdfr_verify_*; 413: the export of training crops, sdfr_crop_*).  A caller built
+ * refined labels, sdfr_mesh_raster and sdfr_verify_*; 413: the export of training crops, sdfr_crop_*; 414: synthetic
+ * bootstrap crops, sdfr_synth_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -1012,6 +1013,38 @@ int sdfr_crop_export(const float* vertices, int64_t V, const int32_t* faces, int
  * counts are 0.  One workgroup per annotation, integer sums in a fixed tree. */
 int sdfr_crop_counts(const uint8_t* mask, const int32_t* owner, const int32_t* windows, const int64_t* poff, int64_t P, const int32_t* boxes,
                      const int64_t* qoff, int64_t Q, const int32_t* flags, int B, int W, int H, int32_t* counts, void* stream);
+
+/*
+ * Synthetic bootstrap crops: colour images of posed shapes of the prior (csrc/synth.hip; DESIGN.md "Synthetic crops").  csrc/synth_cells.h is
+ * the arithmetic, which also compiles for the host.  All pointers are device pointers except K.  The NOCS image of such a crop is
+ * sdfr_crop_export's (colors NULL) and its counts are sdfr_crop_counts', both fed sdfr_synth_owner's owner image.
+ *
+ * sdfr_synth_owner: sdfr_crop_owner with scene int32 [B]: annotation c can own a pixel of annotation b only when scene[c] == scene[b], so
+ *   that several scenes -- different images sharing K and the image size -- go through one launch.  scene == NULL: sdfr_crop_owner's bits.
+ */
+int sdfr_synth_owner(const uint8_t* mask, const float* depth, const int32_t* windows, const int64_t* poff, int64_t P, const int32_t* scene, int B,
+                     int W, int H, int32_t* owner, void* stream);
+/* rgb uint8 [Q][3], packed as sdfr_crop_export packs uvw.  Box pixel (x, y) of annotation b in scene s = scene[b] (0 for scene == NULL): with
+ * c = owner[b's window pixel], if c is an annotation of scene s whose window holds (x, y) and whose winning triangle there is not -1, the
+ * pixel is that triangle shaded, in float64 with every operation rounded separately and dot products summed left to right:
+ *   weights q_i = E_i / Z_i, D = (q0 + q1) + q2 as sdfr_crop_export; n_k = ((q0 n0k + q1 n1k) + q2 n2k) / D over normals float32 [V][3] (camera
+ *   frame); len2 = (n0^2 + n1^2) + n2^2; n = 0 if !(len2 > 0) else n / sqrt(len2); p = ((x - cx) / fx, (y - cy) / fy, 1), v = -(p / sqrt(|p|^2));
+ *   light[s] = l x, y, z, ambient, kd (double [S][5], l taken as given); d = max(0, n.l); h = (l + v) / |l + v| (0 if the length is not positive);
+ *   s = max(0, n.h) squared shin times; paint[c] = albedo r, g, b, ks, shin (double [B][5]; shin truncated to 0 .. 7);
+ *   val_k = albedo_k (ambient + kd d) + ks s; byte = 0 for 255 val <= 0 or NaN, 255 for >= 255, else rint(255 val).
+ * Every other box pixel takes the scene's background: the byte of bg uint8 [NBG][H][W][3] (RGB) number bg_index[s] (int32 [S]) if that is in
+ * 0 .. NBG - 1, else the procedural one from ramp[s] = top r, g, b, bottom r, g, b, amp, seed (int32 [S][8], colours and amp clamped to 0 .. 255):
+ *   clamp(top_k + ((bottom_k - top_k) y) / max(H - 1, 1) + ((hash32(seed, x, y, k) >> 24) amp >> 8) - (amp >> 1), 0, 255), integers only, C
+ *   division; hash32 = high half of mix64(seed ^ mix64((x << 33 | y << 2 | k) 0x9E3779B97F4A7C15 + 1)), mix64 the splitmix64 finaliser.
+ * flags int32 [B]: VERIFY_FLAG_INVALID (2) for an annotation whose window, box, offsets or scene (outside 0 .. S - 1) do not fit, or one of
+ *   whose pixels met a triangle index outside the owner's mesh other than -1 (or a triangle the rasteriser would have skipped); all pixels of
+ *   such an annotation are zeroed.  Nothing is read or written out of bounds for any values in the arrays; nothing outside qoff[b] ..
+ *   qoff[b + 1] is written for annotation b.  Three launches, no memset, no host synchronisation. */
+int sdfr_synth_shade(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const float* normals, const int64_t* voff, const int64_t* toff,
+                     const int32_t* windows, const int64_t* poff, int64_t P, const int32_t* triangle, const int32_t* owner, const int32_t* scene,
+                     const int32_t* boxes, const int64_t* qoff, int64_t Q, const double* paint, const double* light, int S, const int32_t* bg_index,
+                     const uint8_t* bg, int NBG, const int32_t* ramp, int B, int W, int H, const double* K, float z_min, uint8_t* rgb, int32_t* flags,
+                     void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */
