@@ -307,7 +307,7 @@ _NO_GUARD = _NoGuard()
 
 
 TRAFFIC_SOURCES = {          # the csrc files that define the kernels a profiles/traffic_*.json file was measured on (bench.py, tools/summarize_profile.py)
-    "traffic_mlp_forward.json": ("mlp_kernel.h", "mlp.hip", "mlp_fwd32.hip"),
+    "traffic_mlp_forward.json": ("mlp_kernel.h", "kc_slots.h", "mlp.hip", "mlp_fwd32.hip"),
     "traffic_splat.json": ("splat.hip", "splat_bbox.h"),
     "traffic_sphere_step.json": ("trace.hip",),
 }

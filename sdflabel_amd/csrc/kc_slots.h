@@ -1,0 +1,27 @@
+// Slot arithmetic of the KC epilogue (per-tile K compaction of the exact-f32 grid forward, mlp_kernel.h), shared by the kernel
+// and by the host emulation under tests/kc_epilogue_host/.
+//
+// A wave owns 64 consecutive k of the layer it writes.  The full K chain visits them in the order c = 2 q + g (accumulator register
+// q = 0..31, lane group g): the wave's survivors are the set bits of two words, w[g] bit q.  With `off` survivors in the waves in front, the
+// survivor of rank r sits at chain position pos = off + r of the compacted operand: k tile pos / 8, and inside the tile 16-byte vector
+// pos % 2 (the lane group that feeds it to the product), component (pos % 8) / 2.  The operand image is act[vector][point] (16 bytes each).
+//
+// A lane of lane group g holds register q's value at its points; it stores each survivor with 4-byte stores at sdfr_kc_slot(off + rank).
+#pragma once
+#include <stdint.h>
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define SDFR_KC_HD __host__ __device__ __forceinline__
+#else
+#define SDFR_KC_HD inline
+#endif
+
+SDFR_KC_HD int sdfr_kc_popc(uint32_t x) { return __builtin_popcount(x); }
+// chain position -> operand slot (float index inside a point's compacted row: vector slot / 4, component slot % 4)
+SDFR_KC_HD int sdfr_kc_slot(int pos) { return (pos & ~7) | ((pos & 1) * 4) | ((pos & 7) >> 1); }
+// survivors of the wave in front of chain position 2 q + g
+SDFR_KC_HD int sdfr_kc_rank(uint32_t w0, uint32_t w1, int q, int g) {
+    return sdfr_kc_popc(w0 & (uint32_t)((1ull << (q + g)) - 1ull)) + sdfr_kc_popc(w1 & (uint32_t)((1ull << q) - 1ull));
+}
+// the layer's K extent: survivors padded with zero activations (k list entry 0) to a multiple of two k tiles; the LAST wave pads
+SDFR_KC_HD int sdfr_kc_padded(int tot) { return (tot + 15) & ~15; }
+SDFR_KC_HD bool sdfr_kc_pads(int wave, int n_waves) { return wave == n_waves - 1; }

@@ -22,6 +22,7 @@
 //     backwards with the transposed weight image Wb, giving d sdf / d input-row for the selected rows only.
 #pragma once
 #include "sdfr_common.h"
+#include "kc_slots.h"
 #include <math.h>
 #include <type_traits>
 
@@ -303,6 +304,7 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     constexpr bool KC = !HALF && MS == 32 && FT == 2 && (NP == 2 || NP == 1) && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0;
     __shared__ int4 kc_list4[KC ? HP / 4 : 1];                    // operand slot -> k * HP (element offset of the k-row in Wk)
     __shared__ int kc_cnt[KC ? NW : 1];                           // surviving features per wave (published by the layer's first barrier)
+    static_assert(!KC || (KT == 8 && KV == 4), "kc_slots.h: k tiles of 8, vectors of 4");
     static_assert(!KC2 || (KC && sizeof(lds4) + sizeof(jinj) + sizeof(jpfx) + sizeof(kc_list4) + sizeof(kc_cnt) <= 80 * 1024),
                   "KC2: two workgroups per CU, at most 80 KiB of LDS each");
 
@@ -972,13 +974,18 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         // per-group lane-divergent range checks (32 saveexec/branch pairs per layer otherwise).
         const bool inj_here = __builtin_amdgcn_readfirstlane((int)((Ln.inj_n > 0) && !(KGX > KG && P.kinj) && (fbase + MS * FT > inj_lo) &&
                                                                     (fbase < inj_hi))) != 0;
-        // KC, before the barrier: the layer's outputs in place (bias, ReLU, mask bits, re-injected columns) and the wave's 64-bit chain mask --
-        // bit 2q + g for the feature of register q = (f * RG + rg) * 4 + i of lane group g (feature fbase + f MS + rg 8 + 4 g + i), i.e. the
-        // position at which the full K chain visits it inside the wave's 64 k (k tile, component, lane group).  A feature survives when it is
+        // KC, before the barrier: the layer's outputs in place (bias, ReLU, mask bits, re-injected columns) and the wave's two survivor words --
+        // kc_w[g] bit q for the feature of register q = (f * RG + rg) * 4 + i of lane group g (feature fbase + f MS + rg 8 + 4 g + i); 2q + g is
+        // the position at which the full K chain visits it inside the wave's 64 k (k tile, component, lane group).  A feature survives when it is
         // non-zero at some point of the tile; re-injected input columns always do.  kc_cnt[wave] = survivors, published by the barrier.
-        uint64_t kc_cm = 0ull;
+        // The survivor vote costs no ballot per feature: a ReLU output is non-zero exactly where its mask bit is set, so the lane's mask
+        // words already say which of its 32 registers are alive at one of its points; ONE OR-reduction of that word over each lane group
+        // (4 DPP steps inside the rows of 16 lanes, then the four row heads) gives the wave's two survivor words kc_w[g], bit q.  Only the
+        // wave and layer that re-inject input columns force those bits.  (64-row tiles; the 32-row kernel votes by ballot.)
+        uint32_t kc_w[2] = {0u, 0u};
         auto kc_values = [&](auto inj_tag) {
             constexpr bool INJ = decltype(inj_tag)::value;
+            uint32_t injw = 0u;
 #pragma unroll
             for (int f = 0; f < FT; ++f)
 #pragma unroll
@@ -988,31 +995,44 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const bool inj = INJ && j0 + i >= inj_lo && j0 + i < inj_hi;
+                        const int q = (f * RG + rg) * 4 + i;
+                        if (INJ) injw |= (inj ? 1u : 0u) << q;
                         bool nz = inj;
 #pragma unroll
                         for (int p = 0; p < NP; ++p) {
                             const float x = acc[f][p][rg * 4 + i] + f4c(b4, i);
                             const bool pos = x > 0.f;
                             float v = pos ? x : 0.f;
-                            if (SAVE) {
-                                const int bit = ((f * NP + p) * RG + rg) * 4 + i;
-                                mw[bit >> 5] |= (pos ? 1u : 0u) << (bit & 31);
-                            }
+                            const int bit = ((f * NP + p) * RG + rg) * 4 + i;
+                            mw[bit >> 5] |= (pos ? 1u : 0u) << (bit & 31);
                             if (INJ && inj) v = P.inputs[(int64_t)rows[p * MS + lp] * NI + Ln.inj_off + (j0 + i - inj_lo)];
                             acc[f][p][rg * 4 + i] = v;
-                            nz = nz || v != 0.f;
+                            if constexpr (NP == 1) nz = nz || v != 0.f;
                         }
-                        const uint64_t bal = __ballot(nz);
-                        const int q = (f * RG + rg) * 4 + i;
-                        kc_cm |= ((uint64_t)((uint32_t)bal != 0u) << (2 * q)) | ((uint64_t)((bal >> 32) != 0ull) << (2 * q + 1));
+                        if constexpr (NP == 1) {              // 32-row tiles keep the ballot per feature (the word vote costs them 26 more spills)
+                            const uint64_t bal = __ballot(nz);
+                            kc_w[0] |= (uint32_t)((uint32_t)bal != 0u) << q;
+                            kc_w[1] |= (uint32_t)((bal >> 32) != 0ull) << q;
+                        }
                     }
                 }
+            if constexpr (NP == 1) return;
+            // bit q = (f RG + rg) 4 + i: register q's feature is alive at one of this lane's two points
+            uint32_t nzw = ((mw[0] | (mw[0] >> 16)) & 0xffffu) | ((mw[MW - 1] | (mw[MW - 1] >> 16)) << 16);
+            if (INJ) nzw |= injw;
+            int x = (int)nzw;
+            x |= __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, false);      // quad_perm [1, 0, 3, 2]
+            x |= __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, false);      // quad_perm [2, 3, 0, 1]
+            x |= __builtin_amdgcn_update_dpp(0, x, 0x124, 0xf, 0xf, false);     // row_ror:4
+            x |= __builtin_amdgcn_update_dpp(0, x, 0x128, 0xf, 0xf, false);     // row_ror:8
+            kc_w[0] = (uint32_t)(__builtin_amdgcn_readlane(x, 0) | __builtin_amdgcn_readlane(x, 16));
+            kc_w[1] = (uint32_t)(__builtin_amdgcn_readlane(x, 32) | __builtin_amdgcn_readlane(x, 48));
         };
         if constexpr (KC) {
             if (kc_out) {
                 if (inj_here) kc_values(std::true_type{});
                 else kc_values(std::false_type{});
-                if (lane == 0) kc_cnt[wave] = __popcll(kc_cm);
+                if (lane == 0) kc_cnt[wave] = __popc(kc_w[0]) + __popc(kc_w[1]);
             }
         }
         if (!DBUF) __syncthreads();                       // every wave is done reading act (two operand tiles: the epilogue writes the other one)
@@ -1035,7 +1055,6 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             }
             off = __builtin_amdgcn_readfirstlane(off);
             tot = __builtin_amdgcn_readfirstlane(tot);
-            auto slot_of = [](int pos) { return (pos & ~(KT - 1)) | ((pos & 1) * KV) | ((pos & (KT - 1)) >> 1); };
 #pragma unroll
             for (int f = 0; f < FT; ++f)
 #pragma unroll
@@ -1043,25 +1062,26 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int q = (f * RG + rg) * 4 + i;
-                        const int below = __popcll(kc_cm & ((1ull << (2 * q)) - 1ull));
-                        const bool b0 = (kc_cm >> (2 * q)) & 1ull, b1 = (kc_cm >> (2 * q + 1)) & 1ull;
+                        // (wave-uniform: the survivors in front of register q, and whether lane group 0's feature goes first)
+                        const int below = sdfr_kc_rank(kc_w[0], kc_w[1], q, 0);
+                        const bool b0 = (kc_w[0] >> q) & 1u, b1 = (kc_w[1] >> q) & 1u;
                         if (lg ? b1 : b0) {
-                            const int s = slot_of(off + below + ((lg && b0) ? 1 : 0));
+                            const int s = sdfr_kc_slot(off + below + ((lg && b0) ? 1 : 0));
 #pragma unroll
                             for (int p = 0; p < NP; ++p) act_e[((s / KV) * PT + p * MS + lp) * KV + (s % KV)] = acc[f][p][rg * 4 + i];
                         }
                     }
             {   // k list: lane (g, q) enters the feature of register q, lane group g
-                const int q = lp, cl = 2 * q + lg;
-                if ((kc_cm >> cl) & 1ull) {
+                const int q = lp;
+                if ((kc_w[lg] >> q) & 1u) {
                     const int j = fbase + (q >> 4) * MS + ((q >> 2) & 3) * (4 * NLG) + 4 * lg + (q & 3);
-                    reinterpret_cast<int*>(kc_list4)[slot_of(off + __popcll(kc_cm & ((1ull << cl) - 1ull)))] = j * HP;
+                    reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(off + sdfr_kc_rank(kc_w[0], kc_w[1], q, lg))] = j * HP;
                 }
             }
-            const int padded = (tot + 2 * KT - 1) & ~(2 * KT - 1);
-            if (wave == NW - 1) {
+            const int padded = sdfr_kc_padded(tot);
+            if (sdfr_kc_pads(wave, NW)) {
                 for (int e = 0; e < padded - tot; ++e) {
-                    const int s = slot_of(tot + e);
+                    const int s = sdfr_kc_slot(tot + e);
                     if (lane < PT) act_e[((s / KV) * PT + lane) * KV + (s % KV)] = 0.f;       // (lane = point)
                     if (lane == e) reinterpret_cast<int*>(kc_list4)[s] = 0;
                 }
