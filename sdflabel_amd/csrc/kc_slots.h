@@ -7,6 +7,8 @@
 // pos % 2 (the lane group that feeds it to the product), component (pos % 8) / 2.  The operand image is act[vector][point] (16 bytes each).
 //
 // A lane of lane group g holds register q's value at its points; it stores each survivor with 4-byte stores at sdfr_kc_slot(off + rank).
+// (The 32-row kernel.  The 64-row kernels keep this rule for the k list and hold the values in the k-major image at the end of this file;
+// its host emulation is tests/kc_kmajor_host/.)
 #pragma once
 #include <stdint.h>
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -25,3 +27,18 @@ SDFR_KC_HD int sdfr_kc_rank(uint32_t w0, uint32_t w1, int q, int g) {
 // the layer's K extent: survivors padded with zero activations (k list entry 0) to a multiple of two k tiles; the LAST wave pads
 SDFR_KC_HD int sdfr_kc_padded(int tot) { return (tot + 15) & ~15; }
 SDFR_KC_HD bool sdfr_kc_pads(int wave, int n_waves) { return wave == n_waves - 1; }
+
+// The k-major image of the compacted operand (64-row tiles: two point tiles of 32).  The chain order, the ranks and the k list are the ones
+// above; only the place where a survivor's values wait for the product differs.  The survivor at chain position pos owns ROW pos of the
+// image, 64 dwords: point p 32 + lp at dword 2 lp + p, so the two points a lane holds of one feature are neighbours -- one 8-byte store per
+// lane and survivor, 16 lanes cover 32 consecutive dwords.  The product's lane (lp, lg) reads, for k tile t and step ks, the same 8 bytes of
+// row 8 t + 2 ks + lg: the position at which the full chain visits (tile, component, lane group).
+SDFR_KC_HD int sdfr_kcm_dword(int pos, int point) { return pos * 64 + 2 * (point & 31) + (point >> 5); }
+// first dword of the 8 bytes lane lp stores to / reads from row `row`
+SDFR_KC_HD int sdfr_kcm_lane_dword(int row, int lp) { return row * 64 + 2 * lp; }
+SDFR_KC_HD int sdfr_kcm_read_row(int t, int ks, int lg) { return 8 * t + 2 * ks + lg; }
+// padding: rows [tot, padded) are one block of at most 15 x 256 bytes, zeroed by WAVE 0 with four 16-byte stores per lane at most: store i
+// of lane `lane` covers 16-byte vector sdfr_kcm_pad_vec of the image when that lies below 16 padded; lane e < padded - tot enters pad k e
+SDFR_KC_HD bool sdfr_kcm_pads(int wave) { return wave == 0; }
+SDFR_KC_HD int sdfr_kcm_pad_vec(int tot, int i, int lane) { return tot * 16 + i * 64 + lane; }
+constexpr int SDFR_KCM_PAD_STORES = 4;

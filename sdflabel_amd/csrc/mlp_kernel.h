@@ -303,9 +303,13 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     constexpr bool KC2 = sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN, XF>();
     constexpr bool KC = !HALF && MS == 32 && FT == 2 && (NP == 2 || NP == 1) && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0;
     __shared__ int4 kc_list4[KC ? HP / 4 : 1];                    // operand slot -> k * HP (element offset of the k-row in Wk)
-    __shared__ int kc_cnt[KC ? NW : 1];                           // surviving features per wave (published by the layer's first barrier)
-    static_assert(!KC || (KT == 8 && KV == 4), "kc_slots.h: k tiles of 8, vectors of 4");
-    static_assert(!KC2 || (KC && sizeof(lds4) + sizeof(jinj) + sizeof(jpfx) + sizeof(kc_list4) + sizeof(kc_cnt) <= 80 * 1024),
+    __shared__ int4 kc_cnt4[KC ? NW / 4 : 1];                     // surviving features per wave (published by the layer's first barrier)
+    int* kc_cnt = reinterpret_cast<int*>(kc_cnt4);
+    // KM: the compacted operand of the 64-row tiles is the k-major image of kc_slots.h (survivor pos = row pos, a lane's two points side by
+    // side); the 32-row kernel, layer 0's input, the full chain and the last hidden layer's operand keep act[k/KV][point][k%KV]
+    constexpr bool KM = KC && NP == 2;
+    static_assert(!KC || (KT == 8 && KV == 4 && NW == 8), "kc_slots.h: k tiles of 8, vectors of 4, 8 waves");
+    static_assert(!KC2 || (KC && sizeof(lds4) + sizeof(jinj) + sizeof(jpfx) + sizeof(kc_list4) + sizeof(kc_cnt4) <= 80 * 1024),
                   "KC2: two workgroups per CU, at most 80 KiB of LDS each");
 
     const int tid = threadIdx.x;
@@ -789,7 +793,8 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     // s % KV -- the place where the full chain would have visited its feature.  A lane's weight fragments of BOTH feature tiles are gathered
     // as KV 8-byte pairs of the k-major image (Wk[k][sdfr_wk_row(row)]: 32 lanes of a lane group read 256 contiguous bytes per load; with one
     // 4-byte gather per feature tile the loop ran 13 % short of its matrix rate); the k list is read from LDS one tile ahead of
-    // the gather it feeds.  Ring of two tiles and clamped prefetch indices, as in gemm_body's branch-free loop.
+    // the gather it feeds.  Ring of two tiles and clamped prefetch indices, as in gemm_body's branch-free loop.  64-row kernels (KM): the
+    // VALUES of slot s wait in row (s / KT) KT + 2 (s % KV) + (s % KT) / KV of the k-major image (kc_slots.h) -- the same chain position.
     auto gemm_kc_body = [&](const float* __restrict__ Wl, int nk, int nact, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
         const int nkt = nk / KT;
@@ -811,9 +816,20 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             }
         };
         auto load_b = [&](int tile, vec_t* bb) {
-            const vec_t* bp = bptr + tile * (NLG * PT);
+            if constexpr (KM) {
+                // k-major image: step ks of lane group lg is row 8 tile + 2 ks + lg, the lane's 8 bytes hold both point tiles.  Rows two apart
+                // are 512 bytes apart: two paired 8-byte reads with 64-element stride per tile (steps 0, 1 and 2, 3) from one address
 #pragma unroll
-            for (int p = 0; p < NP; ++p) bb[p] = bp[p * MS];
+                for (int ks = 0; ks < KV; ++ks) {
+                    const float2 v = *reinterpret_cast<const float2*>(act_e + sdfr_kcm_lane_dword(sdfr_kcm_read_row(tile, ks, lg), lp));
+                    bb[0][ks] = v.x;
+                    bb[NP - 1][ks] = v.y;
+                }
+            } else {
+                const vec_t* bp = bptr + tile * (NLG * PT);
+#pragma unroll
+                for (int p = 0; p < NP; ++p) bb[p] = bp[p * MS];
+            }
         };
         auto mma = [&](const vec_t* aa, const vec_t* bb) {
 #pragma unroll
@@ -1045,16 +1061,58 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         // KC, after the barrier: the survivors of the waves in front of this one give its first chain position; survivor number `pos` of
         // the layer goes to operand slot (pos / KT) KT + (pos % 2) KV + (pos % KT) / 2 -- k tile, lane group, component of the full chain's
         // order -- and the k list gets its weight row.  The last wave pads the list to a multiple of 2 KT with zero activations (k = 0).
+        // That is the image of the 32-row kernel.  The 64-row kernels (KM) keep the k list's rule and put the VALUES k-major instead: survivor
+        // pos is row pos of 64 dwords, written with 8-byte stores that 16 lanes lay on 32 consecutive dwords (the 4-byte stores at a 16-byte
+        // stride of the other image fall on 8 banks, 4-way), and wave 0 pads.
         auto kc_store = [&]() {
             int off = 0, tot = 0;
+            {
+                const int4 c0 = kc_cnt4[0], c1 = kc_cnt4[KC ? 1 : 0];          // two 16-byte reads, every lane the same address
+                const int c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
 #pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const int c = kc_cnt[w];
-                off += w < wave ? c : 0;
-                tot += c;
+                for (int w = 0; w < 8; ++w) {
+                    off += w < wave ? c[w] : 0;
+                    tot += c[w];
+                }
             }
             off = __builtin_amdgcn_readfirstlane(off);
             tot = __builtin_amdgcn_readfirstlane(tot);
+            if constexpr (KM) {
+                // k-major image (kc_slots.h): the survivor at chain position pos owns row pos; a lane's two points of register q's feature
+                // are neighbours there -- ONE 8-byte store per lane, register and surviving lane group, 16 lanes on 32 consecutive dwords.
+                // The chain position is a running wave-uniform count over q: lane group 0's feature first, then lane group 1's.
+                int n = off;
+#pragma unroll
+                for (int f = 0; f < FT; ++f)
+#pragma unroll
+                    for (int r = 0; r < RG * 4; ++r) {
+                        const int q = f * RG * 4 + r;
+                        const int b0 = (int)((kc_w[0] >> q) & 1u), b1 = (int)((kc_w[1] >> q) & 1u);
+                        if (lg ? b1 : b0)
+                            *reinterpret_cast<float2*>(act_e + sdfr_kcm_lane_dword(n + (lg ? b0 : 0), lp)) = make_float2(acc[f][0][r], acc[f][NP - 1][r]);
+                        n += b0 + b1;
+                    }
+                {   // k list: lane (g, q) enters the feature of register q, lane group g (content and place as without KM)
+                    const int q = lp;
+                    if ((kc_w[lg] >> q) & 1u) {
+                        const int j = fbase + (q >> 4) * MS + ((q >> 2) & 3) * (4 * NLG) + 4 * lg + (q & 3);
+                        reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(off + sdfr_kc_rank(kc_w[0], kc_w[1], q, lg))] = j * HP;
+                    }
+                }
+                // padding: rows [tot, padded) are one block of at most 15 x 256 bytes.  Wave 0 zeroes it (it reaches the epilogue first and
+                // knows tot as every wave does): at most four 16-byte stores per lane, and one predicated store for the pad k entries
+                const int padded = sdfr_kc_padded(tot);
+                if (sdfr_kcm_pads(wave)) {
+#pragma unroll
+                    for (int i = 0; i < SDFR_KCM_PAD_STORES; ++i) {
+                        const int v = sdfr_kcm_pad_vec(tot, i, lane);
+                        if (v < padded * 16) lds4[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+                    if (lane < padded - tot) reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(tot + lane)] = 0;
+                }
+                kc_n = padded;
+                return;
+            }
 #pragma unroll
             for (int f = 0; f < FT; ++f)
 #pragma unroll
