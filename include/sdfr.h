@@ -1047,7 +1047,7 @@ int sdfr_synth_shade(const float* vertices, int64_t V, const int32_t* faces, int
                      void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
- * (2 * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */
+ * (8 waves * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */
 int sdfr_debug_set_trace(void* device_buffer);
 
 #ifdef __cplusplus

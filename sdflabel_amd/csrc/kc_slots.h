@@ -42,3 +42,22 @@ SDFR_KC_HD int sdfr_kcm_read_row(int t, int ks, int lg) { return 8 * t + 2 * ks 
 SDFR_KC_HD bool sdfr_kcm_pads(int wave) { return wave == 0; }
 SDFR_KC_HD int sdfr_kcm_pad_vec(int tot, int i, int lane) { return tot * 16 + i * 64 + lane; }
 constexpr int SDFR_KCM_PAD_STORES = 4;
+
+// The ring of the compacted product loop (gemm_kc_body of the 64-row kernels; host emulation: tests/kc_ring_host).  A layer has nkt k tiles,
+// an even number >= 2 (sdfr_kc_padded).  Tile t is consumed in four chain steps c = 4 t + ks, one per operand component ks, each a group of
+// matrix instructions that reads component ks of the tile's weight fragments.  The fragments have TWO stages (tile t in stage t % 2), and a
+// stage is refilled component by component: right behind chain step (t, ks) the gather of (t + 2, ks) is issued into the registers that step
+// has just read, so that a gather has seven chain steps of lead (1.75 tiles of matrix work; the whole-tile ring gave it four) at no register
+// more.  The k-list words a gather needs have two stages as well: stage t % 2 holds tile t + 2's words while tile t is consumed and reads
+// tile t + 4's behind the tile's last gather; the operand (LDS) of tile t + 1 is read in front of tile t.  Tile indices beyond the last are
+// clamped to it: the tail re-reads the last tile into registers nobody consumes, and the loop (two tiles per trip) has no branch.  Prologue:
+// k list 0 and 1, all gathers of tiles 0 and 1, operand 0, then k list 2 and 3.
+constexpr int SDFR_KC_RING_STAGES = 2, SDFR_KC_RING_LEAD = 2;      // fragment stages; a gather runs this many tiles ahead of its chain step
+SDFR_KC_HD int sdfr_kc_ring_clamp(int tile, int nkt) { return tile < nkt ? tile : nkt - 1; }
+constexpr int sdfr_kc_ring_stage(int t) { return t % SDFR_KC_RING_STAGES; }
+// behind chain step (t, ks): the tile whose component ks is gathered into stage sdfr_kc_ring_stage(t), from k-list stage sdfr_kc_ring_stage(t)
+SDFR_KC_HD int sdfr_kc_ring_gather_tile(int t, int nkt) { return sdfr_kc_ring_clamp(t + SDFR_KC_RING_LEAD, nkt); }
+// behind tile t's last gather: the tile whose k-list words k-list stage sdfr_kc_ring_stage(t) reads
+SDFR_KC_HD int sdfr_kc_ring_klist_tile(int t, int nkt) { return sdfr_kc_ring_clamp(t + 2 * SDFR_KC_RING_LEAD, nkt); }
+// in front of tile t: the tile whose operand is read into operand stage sdfr_kc_ring_stage(t + 1)
+SDFR_KC_HD int sdfr_kc_ring_operand_tile(int t, int nkt) { return sdfr_kc_ring_clamp(t + 1, nkt); }

@@ -146,7 +146,7 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
     return SDFR_OK;
 }
 
-// Debug: device buffer (2 * SDFR_MAX_LAYERS * 5 uint64) that forward kernels built with -DSDFR_MLP_TRACE fill with cycle stamps of their
+// Debug: device buffer (8 waves * SDFR_MAX_LAYERS * 5 uint64) that forward kernels built with -DSDFR_MLP_TRACE fill with cycle stamps of their
 // workgroup 0 (tools/cycle_trace.py); NULL (the default) disables it.  Not part of the renderer path.
 static unsigned long long* g_trace = nullptr;
 extern "C" int sdfr_debug_set_trace(void* device_buffer) { g_trace = (unsigned long long*)device_buffer; return SDFR_OK; }

@@ -320,12 +320,12 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     const int NI = P.n_inputs;
 
 #ifdef SDFR_MLP_TRACE
-    // cycle stamps of workgroup 0, waves 0 and NW-1, lane 0:  trace[(wave ? 1 : 0)][layer][5] = layer start, product loop done, first barrier
+    // cycle stamps of workgroup 0, every wave (at most 8), lane 0:  trace[wave][layer][5] = layer start, product loop done, first barrier
     // passed, epilogue done, second barrier passed (s_memtime ticks = shader cycles)
 #define SDFR_STAMP(l, i)                                                                                                   \
     do {                                                                                                                   \
-        if (P.trace && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wave == 0 || wave == NW - 1))                   \
-            P.trace[((wave ? 1 : 0) * SDFR_MAX_LAYERS + (l)) * 5 + (i)] = __builtin_amdgcn_s_memtime();                    \
+        if (P.trace && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && wave < 8)                                        \
+            P.trace[(wave * SDFR_MAX_LAYERS + (l)) * 5 + (i)] = __builtin_amdgcn_s_memtime();                              \
     } while (0)
 #else
 #define SDFR_STAMP(l, i) do { } while (0)
@@ -793,7 +793,8 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     // s % KV -- the place where the full chain would have visited its feature.  A lane's weight fragments of BOTH feature tiles are gathered
     // as KV 8-byte pairs of the k-major image (Wk[k][sdfr_wk_row(row)]: 32 lanes of a lane group read 256 contiguous bytes per load; with one
     // 4-byte gather per feature tile the loop ran 13 % short of its matrix rate); the k list is read from LDS one tile ahead of
-    // the gather it feeds.  Ring of two tiles and clamped prefetch indices, as in gemm_body's branch-free loop.  64-row kernels (KM): the
+    // the gather it feeds.  Ring of two tiles and clamped prefetch indices, as in gemm_body's branch-free loop (64-row kernels: refilled
+    // component by component, two tiles ahead -- the ring rule of kc_slots.h).  64-row kernels (KM): the
     // VALUES of slot s wait in row (s / KT) KT + 2 (s % KV) + (s % KT) / KV of the k-major image (kc_slots.h) -- the same chain position.
     auto gemm_kc_body = [&](const float* __restrict__ Wl, int nk, int nact, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
@@ -841,6 +842,65 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                         for (int p = 0; p < NP; ++p) acc[f][p] = M::step(aa[f], bb[p], acc[f][p], ks);
                     }
         };
+        if constexpr (KM && FULL) {
+            // 64-row kernels, full-width waves: the ring rule of kc_slots.h (sdfr_kc_ring_*).  A fragment stage is refilled component by
+            // component -- the 8-byte gather of (tile t + 2, component ks) goes out right behind the four matrix instructions that read
+            // component ks of tile t -- so a gather that misses L2 has seven groups of four matrix instructions to land instead of the four
+            // the whole-tile ring gave it, in the same registers.  The layer's first gathers go out before the accumulators are zeroed.
+            // A gather's address is the layer's image (wave-uniform) plus a 32-bit byte offset, (k row + lane's rows) * 4 < 2^21: two 32-bit
+            // VALU instructions per gather where the 64-bit pointer sum took three, one of them a 64-bit add.
+            const uint32_t wlane4 = (uint32_t)(fbase + 2 * lp) * 4u;
+            auto load_a1 = [&](const int4& k, int ks, vec_t* aa) {
+                int kk = ks == 0 ? k.x : ks == 1 ? k.y : ks == 2 ? k.z : k.w;
+#ifdef SDFR_KC_PIN
+                kk &= 8 * HP - 1;     // ablation (timing only, wrong results): the gathers hit L1
+#endif
+                const float2 w = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(Wl) + (uint32_t)((uint32_t)kk * 4u + wlane4));
+                aa[0][ks] = w.x;
+                aa[FT - 1][ks] = w.y;
+            };
+            auto mma1 = [&](const vec_t* aa, const vec_t* bb, int ks) {
+#pragma unroll
+                for (int f = 0; f < FT; ++f)
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) acc[f][p] = M::step(aa[f], bb[p], acc[f][p], ks);
+            };
+            ko[0] = klp[0];
+            ko[1] = klp[sdfr_kc_ring_clamp(1, nkt) * NLG];
+            // (the prologue's gathers are pinned to the loop's order, component by component: the compiler counts its waits over the back
+            // edge against the older of the two orders, and a permuted prologue costs every trip its lead)
+#pragma unroll
+            for (int ks = 0; ks < M::NSTEP; ++ks) { load_a1(ko[0], ks, a[0]); __builtin_amdgcn_sched_barrier(0); }
+            load_b(0, b[0]);
+#pragma unroll
+            for (int ks = 0; ks < M::NSTEP; ++ks) { load_a1(ko[1], ks, a[1]); __builtin_amdgcn_sched_barrier(0); }
+            ko[0] = klp[sdfr_kc_ring_clamp(2, nkt) * NLG];
+            ko[1] = klp[sdfr_kc_ring_clamp(3, nkt) * NLG];
+#pragma unroll
+            for (int f = 0; f < FT; ++f)
+#pragma unroll
+                for (int p = 0; p < NP; ++p)
+#pragma unroll
+                    for (int r = 0; r < RG * 4; ++r) acc[f][p][r] = 0.f;
+            __builtin_amdgcn_sched_barrier(0);
+            for (int t = 0; t < nkt; t += SDFR_KC_RING_STAGES) {
+#pragma unroll
+                for (int u = 0; u < SDFR_KC_RING_STAGES; ++u) {
+                    const int s = sdfr_kc_ring_stage(u), sn = sdfr_kc_ring_stage(u + 1);
+                    load_b(sdfr_kc_ring_operand_tile(t + u, nkt), b[sn]);
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int ks = 0; ks < M::NSTEP; ++ks) {
+                        mma1(a[s], b[s], ks);
+                        __builtin_amdgcn_sched_barrier(0);
+                        load_a1(ko[s], ks, a[s]);                 // (tile sdfr_kc_ring_gather_tile(t + u): its words are in ko[s])
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    ko[s] = klp[sdfr_kc_ring_klist_tile(t + u, nkt) * NLG];
+                }
+            }
+            return;
+        }
         const int last = nkt - 1;
         ko[0] = klp[0];
         load_a(ko[0], a[0]);
@@ -862,15 +922,18 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         }
     };
     auto gemm_kc = [&](auto Wl, int nk, int rows_active) {            // (generic: instantiated by KC kernels only)
-#pragma unroll
-        for (int f = 0; f < FT; ++f)
-#pragma unroll
-            for (int p = 0; p < NP; ++p)
-#pragma unroll
-                for (int r = 0; r < RG * 4; ++r) acc[f][p][r] = 0.f;
         int nact = (rows_active - fbase + MS - 1) / MS;
         nact = nact < 0 ? 0 : (nact > FT ? FT : nact);
         nact = __builtin_amdgcn_readfirstlane(nact);
+        // (64-row kernels: the body zeroes the accumulators itself, behind its first gathers)
+        if (!KM || nact != FT || nk < KT) {
+#pragma unroll
+            for (int f = 0; f < FT; ++f)
+#pragma unroll
+                for (int p = 0; p < NP; ++p)
+#pragma unroll
+                    for (int r = 0; r < RG * 4; ++r) acc[f][p][r] = 0.f;
+        }
         if (nact == FT) gemm_kc_body(Wl, nk, FT, std::true_type{});
         else if (nact > 0) gemm_kc_body(Wl, nk, nact, std::false_type{});
     };
@@ -1148,6 +1211,11 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         };
         auto epilogue = [&](auto inj_tag) {
             constexpr bool INJ = decltype(inj_tag)::value;
+            // 64-row KC kernels: ONE address register per layer for the sixteen 16-byte stores -- the lane's part of the address, made opaque
+            // so that the rest of each address stays a constant the store carries as its offset.  Left to itself the compiler builds the sixteen
+            // addresses with ORs once in the kernel's prologue and keeps them across every product loop (ten of them in scratch).
+            int elane = ((fbase / KV + lg) * PT + lp) * KV;
+            if constexpr (KM) asm volatile("" : "+v"(elane));
 #pragma unroll
             for (int f = 0; f < FT; ++f)
 #pragma unroll
@@ -1176,7 +1244,8 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                                     if (j0 + i >= inj_lo && j0 + i < inj_hi) v[i] = src[j0 + i];
                             }
                         }
-                        store4(actw_e + ((j0 / KV) * PT + pt) * KV + (j0 % KV), v);
+                        if constexpr (KM) store4(actw_e + elane + (((f * MS + rg * 4 * NLG) / KV) * PT + p * MS) * KV, v);
+                        else store4(actw_e + ((j0 / KV) * PT + pt) * KV + (j0 % KV), v);
                     }
                 }
         };

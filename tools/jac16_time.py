@@ -32,17 +32,17 @@ for B in [int(a) for a in sys.argv[1:]] or [int(os.environ.get("SDFR_JAC_B", "64
 print(os.path.basename(os.environ.get("SDFR_LIB", "default")), "flag", FLAG, " | ".join(out))
 if os.environ.get("SDFR_JAC_TRACE"):
     # per-layer cycle stamps of workgroup (0, 0) (library built with SDFR_J16_DEFS=-DSDFR_MLP_TRACE): product loop incl. mask fetch, wait at the
-    # first barrier, mask application + operand store, wait at the second barrier; waves 0 and 7
+    # first barrier, mask application + operand store, wait at the second barrier; the buffer holds every wave (8 x 16 x 5), waves 0 and 7 are printed
     B = int(os.environ.get("SDFR_JAC_B", "64"))
     br = sdflabel_amd.BatchRenderer(dec, 40, K_for(64, 64), (64, 64), B, device=dev)
     br.set_params(torch.full((B,), 0.7, device=dev), torch.tensor([[0.05, 0.02, 3.3]], device=dev).expand(B, 3), torch.tensor([[0.3, -0.5, 0.8]], device=dev).expand(B, 3))
     br.forward(); torch.cuda.synchronize()
-    trace = torch.zeros(2 * 16 * 5, dtype=torch.int64, device=dev)
+    trace = torch.zeros(8 * 16 * 5, dtype=torch.int64, device=dev)
     L.sdfr_debug_set_trace(P(trace))
     L.sdfr_mlp_jacobian(br.handle.h, P(br.inputs), br.G, B, P(br.idx), br.cap, P(br.cnt), P(br.J), P(br.sdf_band), P(br.sdf), P(br.mask_ws), FLAG, sdflabel_amd._lib.stream_ptr())
     torch.cuda.synchronize()
     L.sdfr_debug_set_trace(None)
-    t = trace.cpu().view(2, 16, 5)
+    t = trace.cpu().view(8, 16, 5)[[0, 7]]
     print("layer | wave 0: product  barrier1  epilogue  barrier2 | wave 7: product  barrier1  epilogue  barrier2 | layer total (wave 0)")
     for l in range(7, 0, -1):
         row = []
