@@ -107,6 +107,20 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
                 }
         }
     }
+    // k-major image of the band Jacobian's compacted transposed products (mlp_kernel.h, KCJ): Wkj[k][sdfr_kcj_col(in-feature)] at float offset
+    // 4 off_b of the layer, k = out-feature, zero padded like Wb.  The compacted loop runs every wave at full width, so the image is built (and
+    // the compaction offered) only where every hidden layer's in-width fills the padded width.
+    std::vector<float> Wkj;
+    bool kcj_ok = HP == 512 && !d->has_ln && n_lin >= 3;
+    for (int l = 1; l < n_lin - 1; ++l) kcj_ok = kcj_ok && in_dim[l] == HP;
+    if (kcj_ok) {
+        Wkj.assign((size_t)off_b * 4, 0.f);
+        for (int l = 0; l < n_lin - 1; ++l) {
+            const MlpLayer& L = P.L[l];
+            for (int r = 0; r < L.out_dim; ++r)
+                for (int k = 0; k < L.in_dim; ++k) Wkj[(size_t)L.off_b * 4 + (size_t)r * HP + sdfr_kcj_col(k)] = h_W[l][(size_t)r * L.in_dim + k];
+        }
+    }
     for (int k = 0; k < in_dim[n_lin - 1]; ++k) wl[k] = h_W[n_lin - 1][k];
     P.b_last = h_b[n_lin - 1][0];
 
@@ -141,6 +155,12 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
         P.Wk = d->d_Wk;
         P.kcompact = finite ? 1 : 0;
     }
+    if (!Wkj.empty()) {
+        SDFR_HIP_CHECK(hipMalloc(&d->d_Wkj, Wkj.size() * sizeof(float)));
+        SDFR_HIP_CHECK(hipMemcpy(d->d_Wkj, Wkj.data(), Wkj.size() * sizeof(float), hipMemcpyHostToDevice));
+        P.Wkj = d->d_Wkj;
+        P.jcompact = finite ? 1 : 0;
+    }
     P.Wf = d->d_Wf; P.Wb = d->d_Wb; P.Wh = d->d_Wh; P.Ws = d->d_Ws; P.Wbh = d->d_Wbh; P.bias = d->d_bias; P.w_last = d->d_wlast; P.fwd_np = 2;
     *out = d;
     return SDFR_OK;
@@ -153,7 +173,7 @@ extern "C" int sdfr_debug_set_trace(void* device_buffer) { g_trace = (unsigned l
 
 extern "C" int sdfr_decoder_destroy(sdfr_decoder* d) {
     if (!d) return SDFR_OK;
-    void* bufs[] = {d->d_Wf, d->d_Wb, d->d_Wk, d->d_Wh, d->d_Ws, d->d_Wbh, d->d_bias, d->d_wlast, d->d_lng, d->d_lnb, d->ln_ws};
+    void* bufs[] = {d->d_Wf, d->d_Wb, d->d_Wk, d->d_Wkj, d->d_Wh, d->d_Ws, d->d_Wbh, d->d_bias, d->d_wlast, d->d_lng, d->d_lnb, d->ln_ws};
     for (void* b : bufs) (void)hipFree(b);
     delete d;
     return SDFR_OK;

@@ -1,7 +1,10 @@
 // Band Jacobian, float32, padded hidden width 512; mask-fed (MODE 3) or recomputing (MODE 2).
 //   few crops per launch   16-row tiles (16x16x4 MFMA), 4 waves each owning 128 features (one wave per SIMD): a few thousand band rows of ONE
-//                          crop give ~170 workgroups for 256 CUs; every workgroup streams the whole transposed weight image, so the kernel
-//                          sits between its matrix floor (111 us) and its L2 stream (172 x 7.2 MB): 136 us (8 waves of 64 features: 158 us)
+//                          crop give ~170 workgroups for 256 CUs.  Full K chain: every workgroup streams the whole transposed weight image
+//                          (172 x 7.2 MB) and the kernel sits between its matrix floor (111 us) and that L2 stream: 144 us.  Mask-fed, the
+//                          kernel skips the features whose mask bit is 0 in all 16 rows of the tile (KCJ in mlp_kernel.h, kcj_slots.h): a
+//                          mean of 0.57 of the chain after padding, rows gathered from the k-major image Wkj, 123 us -- the matrix work
+//                          falls with the K extent, the compacting store stage and the slowest tile keep the rest (profiles/jac_kc_notes.md)
 //   many crops per launch  32-row tiles (32x32x2 MFMA, paired K order = the 16-row kernel's, see gemm_pair), 4 waves of 128 features:
 //                          half the weight stream per row, 118 TFLOP/s = 75 % of the f32 MFMA peak at 64 crops (16-row tiles: 93-108)
 // The two return identical bits (same k order, same first-layer partition), so the choice is invisible in the results.
@@ -48,8 +51,12 @@ void sdfr_launch_jac_f32_512(const MlpParams& P, int cap, int B, bool from_masks
         hipLaunchKernelGGL((sdfr_mlp_kernel<float, SDFR_JAC_MS, SDFR_JAC_FT, SDFR_JAC_NP, SDFR_JAC_NW, SDFR_JAC_PF, 3>),
                            dim3(sdfr_cdiv(cap, SDFR_JAC_MS * SDFR_JAC_NP), B), dim3(64 * SDFR_JAC_NW), 0, s, P);
     } else {
+        // SDFR_JAC_COMPACT=0 (read at every launch): the full K chain -- A/B timing and the parity tests; the results are the same bits
+        MlpParams Q = P;
+        const char* e = getenv("SDFR_JAC_COMPACT");
+        if (e && e[0] == '0') Q.jcompact = 0;
         hipLaunchKernelGGL((sdfr_mlp_kernel<float, 16, SDFR_JAC_SMALL_FT, 1, SDFR_JAC_SMALL_NW, SDFR_JAC_SMALL_PF, 3>), dim3(sdfr_cdiv(cap, 16), B),
-                           dim3(64 * SDFR_JAC_SMALL_NW), 0, s, P);
+                           dim3(64 * SDFR_JAC_SMALL_NW), 0, s, Q);
     }
 }
 

@@ -23,6 +23,7 @@
 #pragma once
 #include "sdfr_common.h"
 #include "kc_slots.h"
+#include "kcj_slots.h"
 #include <math.h>
 #include <type_traits>
 
@@ -114,6 +115,8 @@ struct MlpParams {
     float t_eps, t_sigma;
     unsigned long long* t_evals; // += active rays per pass (ray evaluations of the march, for the roofline)
     int32_t* t_unresolved;       // += rays still active when the step budget ran out
+    const float* Wkj;            // exact-f32 backward, k-major image: [layer][k][sdfr_kcj_col(in-feature)] floats at float offset 4 * off_b (KCJ below)
+    int jcompact;                // 1: the 16-row mask-fed Jacobian skips features whose mask bit is 0 in every row of a tile (0: the full K chain)
 };
 
 struct sdfr_decoder {
@@ -122,6 +125,7 @@ struct sdfr_decoder {
     float4* d_Wf;
     float4* d_Wb;
     float* d_Wk;
+    float* d_Wkj;
     void* d_Wh;
     void* d_Ws;
     void* d_Wbh;
@@ -223,6 +227,9 @@ __device__ __forceinline__ int sdfr_mask_shift(int j) { return ((j >> 2) & 1) * 
 template <typename ET, int MS, int FT, int NP, int NW, int MODE, bool LN, int XF> constexpr bool sdfr_mlp_kc2() {
     return sizeof(ET) == 4 && MS == 32 && FT == 2 && NP == 1 && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0;
 }
+template <typename ET, int MS, int FT, int NP, int NW, int MODE, bool LN, int XF> constexpr bool sdfr_mlp_kcj() {
+    return sizeof(ET) == 4 && MS == 16 && NP == 1 && NW == 4 && FT == 8 && MODE == 3 && !LN && XF == 0;
+}
 template <typename ET, int MS, int FT, int NP, int NW, int PF, int MODE, int PFB_ = 0, bool LN = false, int XF = 0>
 __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN, XF>() ? 4 : SDFR_MLP_WPE)) void sdfr_mlp_kernel(const MlpParams P) {
     typedef Mma<ET, MS> M;
@@ -309,6 +316,14 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     // side); the 32-row kernel, layer 0's input, the full chain and the last hidden layer's operand keep act[k/KV][point][k%KV]
     constexpr bool KM = KC && NP == 2;
     static_assert(!KC || (KT == 8 && KV == 4 && NW == 8), "kc_slots.h: k tiles of 8, vectors of 4, 8 waves");
+    // KCJ (K compaction of the band Jacobian's transposed products, 16-row float32 mask-fed kernel; kcj_slots.h): the operand
+    // of a product is g (.) mask, +0 wherever the mask is 0, and the masks are inputs.  store_in_grad keeps only the features whose mask bit
+    // is set in some row of the tile, at consecutive chain positions in the full chain's order; the product walks that list and gathers its
+    // weights from the k-major image Wkj.  A skipped term is fma(+-0, acc) == acc and acc never becomes -0: every bit of J is the full chain's.
+    constexpr bool KCJ = sdfr_mlp_kcj<ET, MS, FT, NP, NW, MODE, LN, XF>();
+    __shared__ int4 kcj_list4[KCJ ? HP / 4 : 1];                  // [k tile][lane group] the four components' k rows (element offsets in Wkj)
+    __shared__ int4 kcj_cnt4[1];                                  // surviving features per wave (published by the barrier behind the product)
+    static_assert(!KCJ || (KT == SDFR_KCJ_KT && PT == SDFR_KCJ_PT && KV == 4 && PF == SDFR_KCJ_RING && MW == 1), "kcj_slots.h: 16-row tiles, k tiles of 16, ring of 4");
     static_assert(!KC2 || (KC && sizeof(lds4) + sizeof(jinj) + sizeof(jpfx) + sizeof(kc_list4) + sizeof(kc_cnt4) <= 80 * 1024),
                   "KC2: two workgroups per CU, at most 80 KiB of LDS each");
 
@@ -937,6 +952,56 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         if (nact == FT) gemm_kc_body(Wl, nk, FT, std::true_type{});
         else if (nact > 0) gemm_kc_body(Wl, nk, nact, std::false_type{});
     };
+    // KCJ product: the operand holds nk compacted chain positions (whole trips of SDFR_KCJ_RING k tiles), in the layout the full chain reads.
+    // Component s of lane group lg in k tile t meets row kcj_list4[4 t + lg][s] of the k-major image Wkj, where the lane's eight feature-tile
+    // values are contiguous (sdfr_kcj_col): two 16-byte gathers per component, eight per tile as in the full chain, the address a 32-bit
+    // offset on the wave-uniform layer image.  The ring of kcj_slots.h: weights three tiles ahead, their k-list words one tile before that,
+    // clamped indices, one block per trip.  (Every wave is full width: the launcher selects the compaction only for hidden in-widths of HP.)
+    auto gemm_kcj = [&](const float* __restrict__ Wl, int nk) {
+        if constexpr (KCJ) {
+        const int nkt = nk / KT;
+        const uint32_t wlane4 = (uint32_t)(fbase + 8 * lp) * 4u;
+        const vec_t* bptr = act + lg * PT + lp;
+        const int4* klp = kcj_list4 + lg;
+        float4 a[SDFR_KCJ_RING][4][2], b[2];
+        auto load_a = [&](const int4& k, float4 (*aa)[2]) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int kk = ks == 0 ? k.x : ks == 1 ? k.y : ks == 2 ? k.z : k.w;
+                const float4* wp = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(Wl) + (uint32_t)((uint32_t)kk * 4u + wlane4));
+                aa[ks][0] = wp[0];
+                aa[ks][1] = wp[1];
+            }
+        };
+        int4 ko = klp[0];
+#pragma unroll
+        for (int u = 0; u < SDFR_KCJ_RING - 1; ++u) {
+            load_a(ko, a[u]);
+            ko = klp[sdfr_kcj_ring_clamp(u + 1, nkt) * NLG];
+        }
+        b[0] = bptr[0];
+#pragma unroll
+        for (int f = 0; f < FT; ++f)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[f][0][r] = 0.f;
+        __builtin_amdgcn_sched_barrier(0);
+        for (int t = 0; t < nkt; t += SDFR_KCJ_RING) {
+#pragma unroll
+            for (int u = 0; u < SDFR_KCJ_RING; ++u) {
+                load_a(ko, a[(u + SDFR_KCJ_RING - 1) % SDFR_KCJ_RING]);       // (tile sdfr_kcj_ring_gather_tile(t + u): its words are in ko)
+                b[(u + 1) % 2] = bptr[sdfr_kcj_ring_operand_tile(t + u, nkt) * (NLG * PT)];
+                ko = klp[sdfr_kcj_ring_klist_tile(t + u, nkt) * NLG];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                    for (int f = 0; f < FT; ++f)
+                        acc[f][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(a[u][ks][f >> 2], f & 3), f4c(b[u % 2], ks), acc[f][0], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        }
+    };
     // first feature of the 4-register group rg of feature tile f held by this lane
     auto feat0 = [&](int f, int rg) { return fbase + f * MS + rg * (4 * NLG) + 4 * lg; };
     const vec_t* Wfwd = reinterpret_cast<const vec_t*>(HALF ? (const void*)P.Wh : (const void*)P.Wf);
@@ -1498,6 +1563,46 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         continue;                                          // the pool's next tile
     }
     if constexpr (JAC) {
+    uint32_t raw[NP * FT * RG];
+    // KCJ: the survivors of the operand store_in_grad(l) is about to write -- the lane's mask word of layer l-1 (bit 4 f + i: feature
+    // fbase + 16 f + 4 lg + i at point lp; features >= prev_out, padding and re-injected input columns, never survive) ORed over the 16 lanes
+    // of each lane group with DPP row steps: kcj_w[g] bit q.  The masks do not depend on the product, so the vote runs in front of the barrier
+    // that follows it anyway and publishes the wave's count there, as the forward publishes kc_cnt.
+    const bool kcj_on = KCJ && P.jcompact && P.Wkj;
+    uint32_t kcj_w[4] = {0u, 0u, 0u, 0u};
+    int kcj_n = 0;                                      // compacted K extent of the operand the next product reads
+    auto kcj_vote = [&](int l, const uint32_t* raw) {
+        const int prev_out = P.L[l - 1].out_dim;
+        uint32_t m = 0u;
+#pragma unroll
+        for (int f = 0; f < FT; ++f) m |= ((raw[f] >> sdfr_mask_shift(fbase + f * MS + 4 * lg)) & 0xFu) << (4 * f);
+        if (__builtin_amdgcn_readfirstlane((int)(fbase + MS * FT > prev_out)) != 0) {
+            uint32_t keep = 0u;
+#pragma unroll
+            for (int f = 0; f < FT; ++f) {
+                const int nv = min(max(prev_out - (fbase + f * MS + 4 * lg), 0), 4);
+                keep |= ((1u << nv) - 1u) << (4 * f);
+            }
+            m &= keep;
+        }
+        int x = (int)m;
+        x |= __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, false);      // quad_perm [1, 0, 3, 2]
+        x |= __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, false);      // quad_perm [2, 3, 0, 1]
+        x |= __builtin_amdgcn_update_dpp(0, x, 0x124, 0xf, 0xf, false);     // row_ror:4
+        x |= __builtin_amdgcn_update_dpp(0, x, 0x128, 0xf, 0xf, false);     // row_ror:8
+#pragma unroll
+        for (int g = 0; g < 4; ++g) kcj_w[g] = (uint32_t)__builtin_amdgcn_readlane(x, 16 * g);
+        if (lane == 0) reinterpret_cast<int*>(kcj_cnt4)[wave] = sdfr_kcj_count(kcj_w[0], kcj_w[1], kcj_w[2], kcj_w[3]);
+    };
+    const bool kcj_top = kcj_on && P.n_mfma >= 2;       // the top operand (of the last hidden layer's product) is compacted: its masks are
+    if constexpr (KCJ) {                                // fetched and voted on in front of the barrier below
+        if (kcj_top) {
+            const int r = rows[lp];
+#pragma unroll
+            for (int f = 0; f < FT; ++f) raw[f] = P.maskbuf[sdfr_mask_dword(r, P.n_mfma - 1, P.n_mfma, HP / 32, fbase + f * MS + 4 * lg)];
+            kcj_vote(P.n_mfma, raw);
+        }
+    }
     __syncthreads();
     SDFR_STAMP(8, 2);
 
@@ -1675,6 +1780,50 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             }
         }
         // 3) operand of the next (previous layer's) transposed product
+        if constexpr (KCJ) {
+            if (kcj_on && l >= 2) {
+                // KCJ (kcj_slots.h): the survivors of the waves in front give this wave's first chain position; a running wave-uniform count
+                // over the registers q, plus the surviving lane groups in front of the lane's own, is a value's chain position.  Layer 0's
+                // product (l == 1) keeps the full operand: its VALU reduction and fixed partition are untouched.
+                const int4 c4 = kcj_cnt4[0];
+                const int c[4] = {c4.x, c4.y, c4.z, c4.w};
+                int off = 0, tot = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    off += w < wave ? c[w] : 0;
+                    tot += c[w];
+                }
+                off = __builtin_amdgcn_readfirstlane(off);
+                tot = __builtin_amdgcn_readfirstlane(tot);
+                const uint32_t mine = lg == 0 ? kcj_w[0] : lg == 1 ? kcj_w[1] : lg == 2 ? kcj_w[2] : kcj_w[3];
+                int n = off;
+#pragma unroll
+                for (int q = 0; q < 32; ++q) {
+                    const int b0 = (int)((kcj_w[0] >> q) & 1u), b1 = (int)((kcj_w[1] >> q) & 1u), b2 = (int)((kcj_w[2] >> q) & 1u),
+                              b3 = (int)((kcj_w[3] >> q) & 1u);
+                    const int front = ((b0 << 2) | ((b0 + b1) << 4) | ((b0 + b1 + b2) << 6)) >> (2 * lg) & 3;      // survivors of q in the lane groups in front
+                    if ((mine >> q) & 1u) act_e[sdfr_kcj_elem(n + front, lp)] = acc[q >> 2][0][q & 3];
+                    n += b0 + b1 + b2 + b3;
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {           // k list: lane (lg, lp) enters the features of registers lp and lp + 16 of its lane group
+                    const int q = lp + 16 * h;
+                    if ((mine >> q) & 1u)
+                        reinterpret_cast<int*>(kcj_list4)[sdfr_kcj_kidx(off + sdfr_kcj_rank(kcj_w[0], kcj_w[1], kcj_w[2], kcj_w[3], q, lg))] =
+                            (fbase + sdfr_kcj_feature(q, lg)) * HP;
+                }
+                // padding: zero operand rows and k-list entries 0 up to whole trips of the product loop (at least one: a layer without a
+                // survivor runs one trip of zeros)
+                const int padded = sdfr_kcj_padded(tot);
+                for (int e = tid; e < (padded - tot) * PT; e += NT) {
+                    const int pos = sdfr_kcj_pad_pos(tot, e);
+                    act_e[sdfr_kcj_elem(pos, sdfr_kcj_pad_point(e))] = 0.f;
+                    if (sdfr_kcj_pad_point(e) == 0) reinterpret_cast<int*>(kcj_list4)[sdfr_kcj_kidx(pos)] = 0;
+                }
+                kcj_n = padded;
+                return;
+            }
+        }
 #pragma unroll
         for (int f = 0; f < FT; ++f)
 #pragma unroll
@@ -1691,8 +1840,7 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     };
 
     // top: in-gradient of the last linear = w_last[k] * gy[pt]
-    uint32_t raw[NP * FT * RG];
-    if (GMASK && !MLDS) fetch_masks(P.n_mfma, raw);
+    if (GMASK && !MLDS && !kcj_top) fetch_masks(P.n_mfma, raw);
     SDFR_STAMP(8, 3);
     if constexpr (MLDS) {
         if (P.n_mfma >= 1 && !(P.n_mfma - 1 == 0 && P.L[0].in_dim <= 8))
@@ -1830,9 +1978,18 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         }
         SDFR_STAMP(l, 0);
         if (GMASK && !MLDS && l > 0) fetch_masks(l, raw);
+        bool kcj_l = false;                                // KCJ: this product reads a compacted operand; the next one's survivors are voted on
+        if constexpr (KCJ) kcj_l = kcj_on && l >= 1;
+        if constexpr (KCJ) {
+            if (kcj_l) gemm_kcj(P.Wkj + (int64_t)L.off_b * 4, kcj_n);
+        }
+        if (!kcj_l)
         gemm(reinterpret_cast<const vec_t*>(HALF ? (const void*)P.Wbh : (const void*)P.Wb) + (HALF ? L.off_bh : L.off_b), HALF ? L.kp_bh : L.kp_b,
              L.in_dim);
         SDFR_STAMP(l, 1);
+        if constexpr (KCJ) {
+            if (kcj_on && l >= 2) kcj_vote(l, raw);
+        }
         __syncthreads();
         SDFR_STAMP(l, 2);
         if (l > 0) {
