@@ -198,7 +198,10 @@ extern "C" int sdfr_scatter_values(float* dst, const float* src, const int32_t* 
 // have just been computed.  dev = max |half-pass value - exact value| over the crop's candidates:
 //   dev > margin / 2   "soft" violation: counted, and the crop's margin grows to 4 * dev for the following selections
 //   dev >= margin      "hard" violation: counted separately -- a row may have been excluded wrongly in THIS step
+// A NaN exact value makes dev NaN, which fails both comparisons: counted soft and hard, the margin kept.
 // Everything stays on the device (no host synchronisation; graph-capturable); the host reads the counters when convenient.
+// (fmaxf returns its non-NaN operand and would drop such a deviation at every stage of the maximum; for NaN-free operands this IS fmaxf)
+__device__ __forceinline__ float sdfr_max_keep_nan(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b); }
 __global__ __launch_bounds__(1024) void sdfr_prefilter_guard_kernel(float* __restrict__ dst, const float* __restrict__ src,
                                                                    const int32_t* __restrict__ idx, int64_t G, int cap,
                                                                    const int32_t* __restrict__ cnt, float* __restrict__ margin,
@@ -211,19 +214,19 @@ __global__ __launch_bounds__(1024) void sdfr_prefilter_guard_kernel(float* __res
         const int64_t e = (int64_t)b * cap + s;
         const int64_t r = (int64_t)b * G + idx[e];
         const float v = src[e];
-        dev = fmaxf(dev, fabsf(dst[r] - v));
+        dev = sdfr_max_keep_nan(dev, fabsf(dst[r] - v));
         dst[r] = v;
     }
-    for (int o = 32; o > 0; o >>= 1) dev = fmaxf(dev, __shfl_xor(dev, o, 64));
+    for (int o = 32; o > 0; o >>= 1) dev = sdfr_max_keep_nan(dev, __shfl_xor(dev, o, 64));
     __shared__ float wmax[16];
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = dev;
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w) dev = fmaxf(dev, wmax[w]);
+        for (int w = 1; w < 16; ++w) dev = sdfr_max_keep_nan(dev, wmax[w]);
         if (reused && reused[b]) return;                  // candidate set reused: the old values were exact ones, not the half pass's
         const float m = margin[b];
         max_dev[b] = dev;
-        if (!(dev <= 0.5f * m)) {                         // also catches NaN
+        if (!(dev <= 0.5f * m)) {                         // also catches NaN (dev keeps one: sdfr_max_keep_nan)
             violations[2 * b] += 1;
             if (!(dev < m)) violations[2 * b + 1] += 1;
             margin[b] = fmaxf(m, 4.f * dev);
