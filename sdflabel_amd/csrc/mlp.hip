@@ -1,6 +1,7 @@
 // DeepSDF decoder: host side of the C ABI (weight packing, dispatch).  The kernels live in mlp_kernel.h and are instantiated in
 // mlp_fwd32.hip / mlp_fwd16.hip / mlp_jac.hip / mlp_small.hip.
 #include "mlp_kernel.h"
+#include <algorithm>
 #include <cmath>
 #include <stdlib.h>
 #include <string.h>
@@ -92,11 +93,15 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
     }
     // k-major image of the exact-f32 grid forward's compacted products (mlp_kernel.h, KC): Wk[k][sdfr_wk_row(row)] at float offset 4 off_f of the
     // layer, zero padded like Wf.  Skipping a zero activation is exact only while 0 * w == 0, i.e. for finite weights: a decoder with an
-    // inf or NaN weight keeps the full K chain.
+    // inf or NaN weight keeps the full K chain.  The 64-row kernels pad a compacted K extent with entries that name row 512 of the layer's
+    // image (kc_slots.h, the zero row of the dense operand): that row must exist and be finite.  Behind every layer but the last it is a
+    // row of a later layer (row 0 of the next one where the layer has its 512 rows); zeros are appended for the rest.
     std::vector<float> Wk;
     bool finite = true;
     if (HP == 512 && !d->has_ln) {
-        Wk.assign((size_t)off_f * 4, 0.f);
+        int64_t wk_floats = off_f * 4;
+        for (int l = 1; l < n_lin - 1; ++l) wk_floats = std::max(wk_floats, sdfr_kcd_wk_floats((int64_t)P.L[l].off_f * 4));
+        Wk.assign((size_t)wk_floats, 0.f);
         for (int l = 0; l < n_lin - 1; ++l) {
             const MlpLayer& L = P.L[l];
             for (int r = 0; r < L.out_dim; ++r)

@@ -20,12 +20,16 @@
 int sdfr_fwd_f32_512_np() { return SDFR_FWD_NP; }
 // What the environment selects, read at every launch (A/B timing and the parity tests).
 //   SDFR_FWD_COMPACT=0   the full K chain instead of the per-tile K compaction (mlp_kernel.h, KC), which is on by default; same bits
+//                        (=2: see fwd_env)
 //   SDFR_FWD_TILE=64/32  Two tile geometries, same bits per row (sdf and mask words): the 64-row tiles with one workgroup per CU
 //                        (the default), and 32-row tiles, 64 KiB of operand, TWO workgroups resident per CU -- one tile's K loop runs under the
 //                        other's epilogue and barriers (mlp_kernel.h, KC2)
 static int fwd_env(MlpParams& Q) {
     const char* e = getenv("SDFR_FWD_COMPACT");
     if (e && e[0] == '0') Q.kcompact = 0;
+    // (=2, tests only: the compaction even where the decoder's finite check declined it -- right only while every non-finite weight sits in
+    // a k row that no survivor and no pad entry names; tests/test_gpu_kc_dense.py shows with it that the row of a dead feature is never read)
+    else if (e && e[0] == '2' && Q.Wk) Q.kcompact = 1;
     int tile = SDFR_FWD_TILE_DEFAULT;
     const char* t = getenv("SDFR_FWD_TILE");
     if (t && t[0] == '6' && t[1] == '4' && !t[2]) tile = 64;

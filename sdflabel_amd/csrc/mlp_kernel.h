@@ -276,7 +276,9 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
 #define SDFR_ACT_DBUF 1
 #endif
     constexpr bool DBUF = SDFR_ACT_DBUF && HALF && !JAC && !LN && !SAVE && (2 * KGX * PT * 16 <= 144 * 1024);
-    constexpr int ACT4 = (DBUF ? 2 : 1) * KGX * PT;
+    // (64-row KC kernels, KM below: the zero row of the dense image, 256 bytes right behind the operand tile -- row 512 of kc_slots.h)
+    constexpr int KZ4 = (!HALF && MS == 32 && FT == 2 && NP == 2 && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0) ? SDFR_KCD_ROW_BYTES / 16 : 0;
+    constexpr int ACT4 = (DBUF ? 2 : 1) * KGX * PT + KZ4;
     // MLDS (r06; the half mask-fed Jacobian on 16x16 products): the ReLU masks of EVERY layer for the tile's rows are fetched once, in the
     // kernel's prologue, and kept in LDS.  Fetched layer by layer in front of each product (r05) the 16 scattered 4-byte gathers per lane sat
     // in front of the layer's first weight fragment in the in-order vmcnt queue (one exposed HBM / L2-miss latency per layer), and unpacking
@@ -309,12 +311,15 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     // (up to the sign of a zero accumulator, which no ReLU output keeps), so every output and mask bit is the full chain's.
     constexpr bool KC2 = sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN, XF>();
     constexpr bool KC = !HALF && MS == 32 && FT == 2 && (NP == 2 || NP == 1) && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0;
-    __shared__ int4 kc_list4[KC ? HP / 4 : 1];                    // operand slot -> k * HP (element offset of the k-row in Wk)
+    __shared__ int4 kc_list4[KC ? HP / 4 : 1];                    // operand slot -> k * HP (element offset of the k-row in Wk; KM: sdfr_kcd_entry)
     __shared__ int4 kc_cnt4[KC ? NW / 4 : 1];                     // surviving features per wave (published by the layer's first barrier)
     int* kc_cnt = reinterpret_cast<int*>(kc_cnt4);
-    // KM: the compacted operand of the 64-row tiles is the k-major image of kc_slots.h (survivor pos = row pos, a lane's two points side by
-    // side); the 32-row kernel, layer 0's input, the full chain and the last hidden layer's operand keep act[k/KV][point][k%KV]
+    // KM: the operand of a compacted layer of the 64-row tiles is the dense k-major image of kc_slots.h (feature j = row j, a lane's two points
+    // side by side; the product reads it through the k list); the 32-row kernel, layer 0's input, the full chain and the last hidden layer's
+    // operand keep act[k/KV][point][k%KV]
     constexpr bool KM = KC && NP == 2;
+    static_assert(KM == (KZ4 != 0) && (!KM || (KGX * PT * 16 == SDFR_KCD_ZERO_ROW * SDFR_KCD_ROW_BYTES && HP == SDFR_KCD_WK_ROW_FLOATS)),
+                  "kc_slots.h: the dense image is 512 rows of 256 bytes, its zero row right behind it");
     static_assert(!KC || (KT == 8 && KV == 4 && NW == 8), "kc_slots.h: k tiles of 8, vectors of 4, 8 waves");
     // KCJ (K compaction of the band Jacobian's transposed products, 16-row float32 mask-fed kernel; kcj_slots.h): the operand
     // of a product is g (.) mask, +0 wherever the mask is 0, and the masks are inputs.  store_in_grad keeps only the features whose mask bit
@@ -810,7 +815,7 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     // 4-byte gather per feature tile the loop ran 13 % short of its matrix rate); the k list is read from LDS one tile ahead of
     // the gather it feeds.  Ring of two tiles and clamped prefetch indices, as in gemm_body's branch-free loop (64-row kernels: refilled
     // component by component, two tiles ahead -- the ring rule of kc_slots.h).  64-row kernels (KM): the
-    // VALUES of slot s wait in row (s / KT) KT + 2 (s % KV) + (s % KT) / KV of the k-major image (kc_slots.h) -- the same chain position.
+    // VALUES of slot s wait in the row of the dense image that the slot's k word names (kc_slots.h, sdfr_kcd_*), pads in the zero row.
     auto gemm_kc_body = [&](const float* __restrict__ Wl, int nk, int nact, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
         const int nkt = nk / KT;
@@ -821,9 +826,11 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         vec_t a[2][FT], b[2][NP];
         int4 ko[2];
         // (KC kernels have FT = 2; Wk keeps a lane's two rows of one k side by side -- sdfr_wk_row --: ONE 8-byte gather per k and lane instead of one per feature tile)
+        // (KM: a k word is the byte offset of the feature's row in the dense image, sdfr_kcd_entry; 2 x that is its float offset in Wk)
+        constexpr int KE = KM ? SDFR_KCD_WK_ROW_FLOATS / SDFR_KCD_ROW_BYTES : 1;
         auto load_a = [&](const int4& k, vec_t* aa) {
-            const float2 w0 = *reinterpret_cast<const float2*>(wp + k.x), w1 = *reinterpret_cast<const float2*>(wp + k.y);
-            const float2 w2 = *reinterpret_cast<const float2*>(wp + k.z), w3 = *reinterpret_cast<const float2*>(wp + k.w);
+            const float2 w0 = *reinterpret_cast<const float2*>(wp + KE * k.x), w1 = *reinterpret_cast<const float2*>(wp + KE * k.y);
+            const float2 w2 = *reinterpret_cast<const float2*>(wp + KE * k.z), w3 = *reinterpret_cast<const float2*>(wp + KE * k.w);
             aa[0][0] = w0.x; aa[0][1] = w1.x; aa[0][2] = w2.x; aa[0][3] = w3.x;
             if (FULL || nact > 1) { aa[FT - 1][0] = w0.y; aa[FT - 1][1] = w1.y; aa[FT - 1][2] = w2.y; aa[FT - 1][3] = w3.y; }
             else {
@@ -831,13 +838,14 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                 for (int i = 0; i < KV; ++i) aa[FT - 1][i] = (ET)0;
             }
         };
-        auto load_b = [&](int tile, vec_t* bb) {
+        auto load_b = [&](int tile, const int4& k, vec_t* bb) {
             if constexpr (KM) {
-                // k-major image: step ks of lane group lg is row 8 tile + 2 ks + lg, the lane's 8 bytes hold both point tiles.  Rows two apart
-                // are 512 bytes apart: two paired 8-byte reads with 64-element stride per tile (steps 0, 1 and 2, 3) from one address
+                // dense image: step ks reads the lane's 8 bytes (both point tiles) of the row its k word names -- four 8-byte reads per
+                // tile, each with its own address, two rows of 256 contiguous bytes per read (one per lane group)
+                const int kw[KV] = {k.x, k.y, k.z, k.w};
 #pragma unroll
                 for (int ks = 0; ks < KV; ++ks) {
-                    const float2 v = *reinterpret_cast<const float2*>(act_e + sdfr_kcm_lane_dword(sdfr_kcm_read_row(tile, ks, lg), lp));
+                    const float2 v = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(act_e) + sdfr_kcd_operand_byte(kw[ks], lp));
                     bb[0][ks] = v.x;
                     bb[NP - 1][ks] = v.y;
                 }
@@ -864,15 +872,20 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             // the whole-tile ring gave it, in the same registers.  The layer's first gathers go out before the accumulators are zeroed.
             // A gather's address is the layer's image (wave-uniform) plus a 32-bit byte offset, (k row + lane's rows) * 4 < 2^21: two 32-bit
             // VALU instructions per gather where the 64-bit pointer sum took three, one of them a 64-bit add.
+            // The operand travels with the weights (sdfr_kcd_ring_operand_tile): the same k word gives the lane's 8 bytes of the dense image's
+            // row, one VALU instruction for either address, read into the operand registers the chain step has just consumed.
             const uint32_t wlane4 = (uint32_t)(fbase + 2 * lp) * 4u;
-            auto load_a1 = [&](const int4& k, int ks, vec_t* aa) {
+            auto load_a1 = [&](const int4& k, int ks, vec_t* aa, vec_t* bb) {
                 int kk = ks == 0 ? k.x : ks == 1 ? k.y : ks == 2 ? k.z : k.w;
 #ifdef SDFR_KC_PIN
-                kk &= 8 * HP - 1;     // ablation (timing only, wrong results): the gathers hit L1
+                kk &= 8 * SDFR_KCD_ROW_BYTES - 1;     // ablation (timing only, wrong results): the gathers hit L1
 #endif
-                const float2 w = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(Wl) + (uint32_t)((uint32_t)kk * 4u + wlane4));
+                const float2 w = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(Wl) + (uint32_t)(sdfr_kcd_weight_byte(kk) + wlane4));
+                const float2 v = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(act_e) + sdfr_kcd_operand_byte(kk, lp));
                 aa[0][ks] = w.x;
                 aa[FT - 1][ks] = w.y;
+                bb[0][ks] = v.x;
+                bb[NP - 1][ks] = v.y;
             };
             auto mma1 = [&](const vec_t* aa, const vec_t* bb, int ks) {
 #pragma unroll
@@ -885,10 +898,9 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             // (the prologue's gathers are pinned to the loop's order, component by component: the compiler counts its waits over the back
             // edge against the older of the two orders, and a permuted prologue costs every trip its lead)
 #pragma unroll
-            for (int ks = 0; ks < M::NSTEP; ++ks) { load_a1(ko[0], ks, a[0]); __builtin_amdgcn_sched_barrier(0); }
-            load_b(0, b[0]);
+            for (int ks = 0; ks < M::NSTEP; ++ks) { load_a1(ko[0], ks, a[0], b[0]); __builtin_amdgcn_sched_barrier(0); }
 #pragma unroll
-            for (int ks = 0; ks < M::NSTEP; ++ks) { load_a1(ko[1], ks, a[1]); __builtin_amdgcn_sched_barrier(0); }
+            for (int ks = 0; ks < M::NSTEP; ++ks) { load_a1(ko[1], ks, a[1], b[1]); __builtin_amdgcn_sched_barrier(0); }
             ko[0] = klp[sdfr_kc_ring_clamp(2, nkt) * NLG];
             ko[1] = klp[sdfr_kc_ring_clamp(3, nkt) * NLG];
 #pragma unroll
@@ -901,14 +913,12 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             for (int t = 0; t < nkt; t += SDFR_KC_RING_STAGES) {
 #pragma unroll
                 for (int u = 0; u < SDFR_KC_RING_STAGES; ++u) {
-                    const int s = sdfr_kc_ring_stage(u), sn = sdfr_kc_ring_stage(u + 1);
-                    load_b(sdfr_kc_ring_operand_tile(t + u, nkt), b[sn]);
-                    __builtin_amdgcn_sched_barrier(0);
+                    const int s = sdfr_kc_ring_stage(u);
 #pragma unroll
                     for (int ks = 0; ks < M::NSTEP; ++ks) {
                         mma1(a[s], b[s], ks);
                         __builtin_amdgcn_sched_barrier(0);
-                        load_a1(ko[s], ks, a[s]);                 // (tile sdfr_kc_ring_gather_tile(t + u): its words are in ko[s])
+                        load_a1(ko[s], ks, a[s], b[s]);           // (tile sdfr_kc_ring_gather_tile(t + u): its words are in ko[s])
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     ko[s] = klp[sdfr_kc_ring_klist_tile(t + u, nkt) * NLG];
@@ -919,17 +929,17 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         const int last = nkt - 1;
         ko[0] = klp[0];
         load_a(ko[0], a[0]);
-        load_b(0, b[0]);
+        load_b(0, ko[0], b[0]);
         ko[1] = klp[min(1, last) * NLG];
         for (int t = 0; t < nkt; t += 2) {
             load_a(ko[1], a[1]);
-            load_b(min(t + 1, last), b[1]);
+            load_b(min(t + 1, last), ko[1], b[1]);
             ko[0] = klp[min(t + 2, last) * NLG];
             __builtin_amdgcn_sched_barrier(0);
             mma(a[0], b[0]);
             __builtin_amdgcn_sched_barrier(0);
             load_a(ko[0], a[0]);
-            load_b(min(t + 2, last), b[0]);
+            load_b(min(t + 2, last), ko[0], b[0]);
             ko[1] = klp[min(t + 3, last) * NLG];
             __builtin_amdgcn_sched_barrier(0);
             mma(a[1], b[1]);
@@ -1088,6 +1098,10 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     int* t_more = reinterpret_cast<int*>(gy);           // gy is unused by forward modes
     const bool kc_on = KC && P.kcompact && P.Wk;
     int kc_n = 0;                                       // KC: compacted K extent of the operand the next product reads
+    if constexpr (KM) {
+        // the zero row of the dense image, written once per workgroup (layer 0's barriers lie between this store and its first reader)
+        if (kc_on && tid < KZ4) lds4[KGX * PT + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     do {
     for (int l = 0; !GMASK && l < P.n_mfma; ++l) {
         const MlpLayer L = P.L[l];
@@ -1189,9 +1203,9 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         // KC, after the barrier: the survivors of the waves in front of this one give its first chain position; survivor number `pos` of
         // the layer goes to operand slot (pos / KT) KT + (pos % 2) KV + (pos % KT) / 2 -- k tile, lane group, component of the full chain's
         // order -- and the k list gets its weight row.  The last wave pads the list to a multiple of 2 KT with zero activations (k = 0).
-        // That is the image of the 32-row kernel.  The 64-row kernels (KM) keep the k list's rule and put the VALUES k-major instead: survivor
-        // pos is row pos of 64 dwords, written with 8-byte stores that 16 lanes lay on 32 consecutive dwords (the 4-byte stores at a 16-byte
-        // stride of the other image fall on 8 banks, 4-way), and wave 0 pads.
+        // That is the image of the 32-row kernel.  The 64-row kernels (KM) keep the k list's places and order and do NOT compact the values:
+        // every feature goes to its own row of 64 dwords (the dense image of kc_slots.h), the k list names rows, and wave 0 pads the list
+        // with the zero row.  The product needs the list of survivors only -- it walks it anyway for its weights.
         auto kc_store = [&]() {
             int off = 0, tot = 0;
             {
@@ -1206,37 +1220,31 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             off = __builtin_amdgcn_readfirstlane(off);
             tot = __builtin_amdgcn_readfirstlane(tot);
             if constexpr (KM) {
-                // k-major image (kc_slots.h): the survivor at chain position pos owns row pos; a lane's two points of register q's feature
-                // are neighbours there -- ONE 8-byte store per lane, register and surviving lane group, 16 lanes on 32 consecutive dwords.
-                // The chain position is a running wave-uniform count over q: lane group 0's feature first, then lane group 1's.
-                int n = off;
+                // dense image (kc_slots.h, sdfr_kcd_*): feature j owns row j, a lane's two points of register q's feature are neighbours
+                // there.  32 unconditional 8-byte stores from ONE address register (the lane's part, made opaque so that each register's row
+                // stays the store's immediate offset); dead features store their zeros, and no survivor word is looked at.  16 lanes lie on
+                // 32 consecutive dwords, lane group 1 writes the row 4 further.
+                {
+                    int dl = sdfr_kcm_lane_dword(sdfr_kcd_row(fbase + sdfr_kcd_row_lane(0, lg)), lp);
+                    asm volatile("" : "+v"(dl));
 #pragma unroll
-                for (int f = 0; f < FT; ++f)
+                    for (int f = 0; f < FT; ++f)
 #pragma unroll
-                    for (int r = 0; r < RG * 4; ++r) {
-                        const int q = f * RG * 4 + r;
-                        const int b0 = (int)((kc_w[0] >> q) & 1u), b1 = (int)((kc_w[1] >> q) & 1u);
-                        if (lg ? b1 : b0)
-                            *reinterpret_cast<float2*>(act_e + sdfr_kcm_lane_dword(n + (lg ? b0 : 0), lp)) = make_float2(acc[f][0][r], acc[f][NP - 1][r]);
-                        n += b0 + b1;
-                    }
-                {   // k list: lane (g, q) enters the feature of register q, lane group g (content and place as without KM)
+                        for (int r = 0; r < RG * 4; ++r)
+                            *reinterpret_cast<float2*>(act_e + dl + sdfr_kcm_lane_dword(sdfr_kcd_row_reg(f * RG * 4 + r), 0)) =
+                                make_float2(acc[f][0][r], acc[f][NP - 1][r]);
+                }
+                {   // k list: lane (g, q) enters the row of register q's feature, lane group g, at the place the chain order gives it
                     const int q = lp;
                     if ((kc_w[lg] >> q) & 1u) {
-                        const int j = fbase + (q >> 4) * MS + ((q >> 2) & 3) * (4 * NLG) + 4 * lg + (q & 3);
-                        reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(off + sdfr_kc_rank(kc_w[0], kc_w[1], q, lg))] = j * HP;
+                        const int j = fbase + sdfr_kcd_feature(0, q, lg);
+                        reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(off + sdfr_kc_rank(kc_w[0], kc_w[1], q, lg))] = sdfr_kcd_entry(j);
                     }
                 }
-                // padding: rows [tot, padded) are one block of at most 15 x 256 bytes.  Wave 0 zeroes it (it reaches the epilogue first and
-                // knows tot as every wave does): at most four 16-byte stores per lane, and one predicated store for the pad k entries
+                // padding: the k entries [tot, padded) name the zero row (one predicated store of wave 0); nothing is stored to the image
                 const int padded = sdfr_kc_padded(tot);
                 if (sdfr_kcm_pads(wave)) {
-#pragma unroll
-                    for (int i = 0; i < SDFR_KCM_PAD_STORES; ++i) {
-                        const int v = sdfr_kcm_pad_vec(tot, i, lane);
-                        if (v < padded * 16) lds4[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-                    if (lane < padded - tot) reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(tot + lane)] = 0;
+                    if (lane < padded - tot) reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(tot + lane)] = sdfr_kcd_pad_entry();
                 }
                 kc_n = padded;
                 return;
