@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 414        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 415        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -45,7 +45,7 @@ extern "C" {
  * sdfr_lidar_normals and sdfr_depth_map_masked; 409: the training-crop augmentation, sdfr_augment; 410: the grid forward with the caller's tile order,
  * sdfr_grid_tile_order and sdfr_mlp_forward_ordered; 411: triangle meshes, sdfr_mesh_*; 412: verification of
  * refined labels, sdfr_mesh_raster and sdfr_verify_*; 413: the export of training crops, sdfr_crop_*; 414: synthetic
- * bootstrap crops, sdfr_synth_*).  A caller built
+ * bootstrap crops, sdfr_synth_*; 415: signed distances to meshes and surface samples, sdfr_mesh_sdf* and sdfr_mesh_surface_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -1045,6 +1045,52 @@ int sdfr_synth_shade(const float* vertices, int64_t V, const int32_t* faces, int
                      const int32_t* boxes, const int64_t* qoff, int64_t Q, const double* paint, const double* light, int S, const int32_t* bg_index,
                      const uint8_t* bg, int NBG, const int32_t* ramp, int B, int W, int H, const double* K, float z_min, uint8_t* rgb, int32_t* flags,
                      void* stream);
+
+/*
+ * Signed distances from query points to triangle meshes, and area-weighted points on their surfaces (csrc/mesh_sdf.hip; DESIGN.md "Signed
+ * distances to meshes").  csrc/mesh_sdf_cells.h is the arithmetic -- its comment fixes the component order of every dot and cross product --
+ * and also compiles for the host.  All pointers are device pointers.  Meshes are packed as sdfr_mesh_raster takes them: vertices float32
+ * [V][3], faces int32 [T][3] with indices local to the mesh, voff / toff int64 [B + 1].
+ *
+ * sdfr_mesh_sdf: points float32 [N][3] with qoff int64 [B + 1], the run of query points of each mesh.  All pairs of a mesh's points and
+ *   triangles, float64 on the float32 values, every operation rounded separately.
+ *   distance   d2(p, tri) = min over the three edges of the squared distance to the segment (t = l2 > 0 ? ap.ab / l2 : 0 clamped to [0, 1]) and,
+ *              when the triangle has area (nn = n.n > 0, n = (b - a) x (c - a)) and p projects into it (the three edge tests >= 0),
+ *              ((p - a).n)^2 / nn.  Zero-area triangles act as segments or points.
+ *   nearest    the minimum of d2 over the mesh's triangles, on equal d2 the lowest index; dist = (float) sqrt(d2)
+ *   winding    the sum of omega = det == 0 ? 0 : atan2(det, den) / (2 pi) (van Oosterom and Strackee) over the triangles
+ *   order      triangles are cut into chunks of 4096 in index order; minimum and sum are taken sequentially inside a chunk (from +inf and
+ *              0) and the chunk results are folded in chunk order.  A function of T alone: the launch shape does not change a bit.
+ *   sign       inside when want_sign and |winding| >= 0.5; sdf = inside ? -dist : dist.  want_sign = 0 skips the winding pass: the unsigned
+ *              distance, for open meshes; winding is then 0.
+ *   skipped    a triangle with a non-finite vertex (flag bit 0) or a face index outside its mesh (flag bit 1); a mesh whose vertex or
+ *              triangle offsets do not fit the arrays (flag bit 1).  A point of a mesh with no usable triangle, a non-finite point, and a
+ *              point outside every usable run of qoff get dist = sdf = +inf, d2 = +inf, nearest = -1, winding = 0.
+ *   outputs    sdf float32 [N]; dist float32 [N], d2 float64 [N], nearest int32 [N] (index within the mesh), winding float64 [N]: each of
+ *              these four may be NULL; flags int32 [B].
+ *   ws         sdfr_mesh_sdf_ws_bytes(B, N, T) bytes, 8-byte aligned (-1: sizes out of range; all of B < 2^24, V, T, N < 2^31).
+ * No atomics, no floating-point reduction across lanes: the same bits on every run, and a mesh's results do not depend on B or on its
+ * position in the batch.  Two launches (three in the chunk-split shape for few points and many triangles), no memset.
+ */
+int64_t sdfr_mesh_sdf_ws_bytes(int B, int64_t N, int64_t T);
+int sdfr_mesh_sdf(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const int64_t* voff, const int64_t* toff,
+                  const float* points, int64_t N, const int64_t* qoff, int B, int want_sign, void* ws, int64_t ws_bytes, float* sdf, float* dist,
+                  double* d2, int32_t* nearest, double* winding, int32_t* flags, void* stream);
+/* Area-weighted surface points from uniforms the caller drew: uniforms float32 [S][3] in [0, 1) with soff int64 [B + 1] the meshes' sample
+ * runs (soff[0] = 0, soff[B] = S, non-decreasing).
+ *   area       area_t = sqrt(nn) / 2 in float64, 0 for a skipped triangle.  local = the sequential running sum inside chunks of 256 triangles,
+ *              base = the sequential exclusive running sum of the chunk totals, cum[t] = base[t / 256] + local[t].
+ *   sample     the triangle is the first t with cum[t] > u0 cum[T - 1] (never one of zero area); s = sqrt(u1), w0 = 1 - s, w1 = s (1 - u2),
+ *              w2 = s u2, x_k = (float)((w0 a_k + w1 b_k) + w2 c_k).
+ *   outputs    points float32 [S][3], triangle int32 [S] (index within the mesh), flags int32 [B]: the bits of sdfr_mesh_sdf, and bit 1 for a
+ *              mesh of zero total area.  Samples of such a mesh, and samples whose uniforms are not all in [0, 1), get triangle = -1 and
+ *              zero points.
+ *   ws         sdfr_mesh_surface_ws_bytes(B, T) bytes, 8-byte aligned.
+ * Four launches, no atomics, no memset. */
+int64_t sdfr_mesh_surface_ws_bytes(int B, int64_t T);
+int sdfr_mesh_surface_points(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const int64_t* voff, const int64_t* toff,
+                             const float* uniforms, int64_t S, const int64_t* soff, int B, void* ws, int64_t ws_bytes, float* points,
+                             int32_t* triangle, int32_t* flags, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (8 waves * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

@@ -1,6 +1,6 @@
 """Triangle meshes of refined DeepSDF shapes, extracted on the device (csrc/mesh.hip; DESIGN.md "Meshes").
 
-    from sdflabel_amd.mesh import mesh_from_sdf, meshes_many, Mesh, load_ply
+    from sdflabel_amd.mesh import mesh_from_sdf, meshes_many, Mesh, load_ply, load_obj
 
 mesh_from_sdf    the iso-surface kernels alone, on SDF samples the caller supplies on the regular lattice
 meshes_many      decoder over the lattice in row chunks -> count -> ONE host read of the totals -> emit -> (polish: decoder, Jacobian and
@@ -98,6 +98,12 @@ class Mesh:
         out.lattice_vertices = self.vertices                   # the vertex order is kept: the NOCS attributes of the camera-frame mesh
         return out
 
+    def signed_distance(self, points, want_sign=True):
+        """float32 [n] on the device: the signed distance of points [n][3] (device tensor, this mesh's frame) to this mesh; negative inside.
+        The one-mesh form of sdf_samples.mesh_sdf_many (`.sdf` is taken: it holds the lattice samples)."""
+        from .sdf_samples import mesh_sdf_many
+        return mesh_sdf_many([self], [points], want_sign=want_sign).sdf
+
     def save(self, path, drop_degenerate=False):
         """binary little-endian PLY (with normals when the mesh has them) or OBJ, by extension.  Host code."""
         v, n, f = self.vertices_numpy(), self.normals_numpy(), self.faces_numpy(drop_degenerate)
@@ -172,6 +178,43 @@ def load_ply(path):
     v = np.ascontiguousarray(vert[:, [props.index(c) for c in "xyz"]], dtype=np.float32)
     n = np.ascontiguousarray(vert[:, [props.index(c) for c in ("nx", "ny", "nz")]], dtype=np.float32) if "nx" in props else None
     return v, n, np.ascontiguousarray(rec["i"], dtype=np.int32)
+
+
+def load_obj(path):
+    """(vertices float32 [V][3], normals float32 [V][3] or None, faces int32 [T][3]) of a Wavefront OBJ: `v` and `f` lines (and `vn`), polygons
+    fanned from their first vertex, indices 1-based or negative (relative to the vertices read so far), `a/b/c` forms accepted.  The normals
+    are returned only when there is one per vertex and every corner names the same index for both, as Mesh.save writes them."""
+    v, vn, faces = [], [], []
+    per_vertex = True
+    with open(path, "r") as fh:
+        for ln in fh:
+            w = ln.split("#")[0].split()
+            if not w:
+                continue
+            if w[0] == "v":
+                v.append([float(x) for x in w[1:4]])
+            elif w[0] == "vn":
+                vn.append([float(x) for x in w[1:4]])
+            elif w[0] == "f":
+                idx = []
+                for c in w[1:]:
+                    parts = c.split("/")
+                    i = int(parts[0])
+                    i = i - 1 if i > 0 else len(v) + i
+                    if not 0 <= i < len(v):
+                        raise ValueError("load_obj: face index %s outside the %d vertices read so far" % (parts[0], len(v)))
+                    if len(parts) == 3 and parts[2]:
+                        k = int(parts[2])
+                        per_vertex &= (k - 1 if k > 0 else len(vn) + k) == i
+                    else:
+                        per_vertex = False
+                    idx.append(i)
+                if len(idx) < 3:
+                    raise ValueError("load_obj: a face with fewer than three vertices")
+                faces += [(idx[0], idx[k], idx[k + 1]) for k in range(1, len(idx) - 1)]
+    vert = np.asarray(v, dtype=np.float32).reshape(-1, 3)
+    nrm = np.asarray(vn, dtype=np.float32).reshape(-1, 3) if per_vertex and vn and len(vn) == len(v) else None
+    return vert, nrm, np.asarray(faces, dtype=np.int32).reshape(-1, 3)
 
 
 # ---- extraction ----------------------------------------------------------------------------------------------------------------------------
