@@ -7,8 +7,9 @@
 // pos % 2 (the lane group that feeds it to the product), component (pos % 8) / 2.  The operand image is act[vector][point] (16 bytes each).
 //
 // A lane of lane group g holds register q's value at its points; it stores each survivor with 4-byte stores at sdfr_kc_slot(off + rank).
-// (The 32-row kernel.  The 64-row kernels keep this rule for the places of the k list and hold the values of EVERY feature in the dense
-// k-major image at the end of this file; its host emulation is tests/kc_dense_host/.)
+// (No kernel writes this compacted value image any more; tests/kc_epilogue_host still walks it.  Its slot, rank and padding rule remains
+// the k list's: the kernels enter a survivor's k word at sdfr_kc_slot(off + rank) and hold the values of EVERY feature in the dense k-major
+// image at the end of this file, whose host emulation is tests/kc_dense_host/.)
 #pragma once
 #include <stdint.h>
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -24,7 +25,8 @@ SDFR_KC_HD int sdfr_kc_slot(int pos) { return (pos & ~7) | ((pos & 1) * 4) | ((p
 SDFR_KC_HD int sdfr_kc_rank(uint32_t w0, uint32_t w1, int q, int g) {
     return sdfr_kc_popc(w0 & (uint32_t)((1ull << (q + g)) - 1ull)) + sdfr_kc_popc(w1 & (uint32_t)((1ull << q) - 1ull));
 }
-// the layer's K extent: survivors padded with zero activations (k list entry 0) to a multiple of two k tiles; the LAST wave pads
+// the layer's K extent: survivors padded with zero activations to a multiple of two k tiles (the kernels: sdfr_kcd_pad_entry, entered by
+// sdfr_kcm_pads' wave).  The compacted value image of tests/kc_epilogue_host: k list entry 0, zeros stored by the LAST wave
 SDFR_KC_HD int sdfr_kc_padded(int tot) { return (tot + 15) & ~15; }
 SDFR_KC_HD bool sdfr_kc_pads(int wave, int n_waves) { return wave == n_waves - 1; }
 
@@ -33,8 +35,9 @@ SDFR_KC_HD bool sdfr_kc_pads(int wave, int n_waves) { return wave == n_waves - 1
 // image, 64 dwords: point p 32 + lp at dword 2 lp + p, so the two points a lane holds of one feature are neighbours -- one 8-byte store per
 // lane and survivor, 16 lanes cover 32 consecutive dwords.  The product's lane (lp, lg) reads, for k tile t and step ks, the same 8 bytes of
 // row 8 t + 2 ks + lg: the position at which the full chain visits (tile, component, lane group).
-// (Of the sdfr_kcm_* functions the 64-row kernels still use sdfr_kcm_lane_dword alone: their operand is the dense image below.  The others
-// stay because tests/kc_kmajor_host and tests/kc_ring_host compile them; removing them is a later change that touches those tests.)
+// (Of the sdfr_kcm_* functions the kernels still use sdfr_kcm_lane_dword and sdfr_kcm_pads alone: their operand is the dense image below.
+// The others stay because tests/kc_kmajor_host and tests/kc_ring_host compile them; removing them is a later change that touches those
+// tests.)
 SDFR_KC_HD int sdfr_kcm_dword(int pos, int point) { return pos * 64 + 2 * (point & 31) + (point >> 5); }
 // first dword of the 8 bytes lane lp stores to / reads from row `row`
 SDFR_KC_HD int sdfr_kcm_lane_dword(int row, int lp) { return row * 64 + 2 * lp; }
@@ -45,7 +48,7 @@ SDFR_KC_HD bool sdfr_kcm_pads(int wave) { return wave == 0; }
 SDFR_KC_HD int sdfr_kcm_pad_vec(int tot, int i, int lane) { return tot * 16 + i * 64 + lane; }
 constexpr int SDFR_KCM_PAD_STORES = 4;
 
-// The ring of the compacted product loop (gemm_kc_body of the 64-row kernels; host emulation: tests/kc_ring_host).  A layer has nkt k tiles,
+// The ring of the compacted product loop (gemm_kc_body, full-width waves; host emulation: tests/kc_ring_host).  A layer has nkt k tiles,
 // an even number >= 2 (sdfr_kc_padded).  Tile t is consumed in four chain steps c = 4 t + ks, one per operand component ks, each a group of
 // matrix instructions that reads component ks of the tile's weight fragments.  The fragments have TWO stages (tile t in stage t % 2), and a
 // stage is refilled component by component: right behind chain step (t, ks) the gather of (t + 2, ks) is issued into the registers that step
@@ -66,7 +69,7 @@ SDFR_KC_HD int sdfr_kc_ring_klist_tile(int t, int nkt) { return sdfr_kc_ring_cla
 // in front of tile t: the tile whose operand is read into operand stage sdfr_kc_ring_stage(t + 1)
 SDFR_KC_HD int sdfr_kc_ring_operand_tile(int t, int nkt) { return sdfr_kc_ring_clamp(t + 1, nkt); }
 
-// The DENSE image of the 64-row kernels (host emulation: tests/kc_dense_host).  The product needs the LIST of survivors, not their values in
+// The DENSE image the kernels use (host emulation: tests/kc_dense_host).  The product needs the LIST of survivors, not their values in
 // consecutive rows: it walks the k list anyway to gather its weights.  So the epilogue writes EVERY feature j of the layer to its own row j
 // of the k-major image (64 dwords, sdfr_kcm_lane_dword(j, lp) = the lane's 8 bytes; dead features store their zeros) -- 32 unconditional
 // 8-byte stores per lane from one address register -- and the k list, whose places, order and padding are the rule at the top of this file,

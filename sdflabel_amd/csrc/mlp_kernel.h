@@ -221,17 +221,16 @@ __device__ __forceinline__ int sdfr_mask_shift(int j) { return ((j >> 2) & 1) * 
 //      4 ORDER    (mlp_fwd32.hip) slot j of the launch evaluates row (j / G) G + order[j % G] (P.gather_idx = order, P.gather_rows = G rows per
 //                 crop): which rows share a tile is the caller's choice -- 4x4x4 blocks of the grid keep fewer features alive per tile than 64
 //                 consecutive rows (KC below).  Values and masks are stored at the ROW, so every consumer reads them as before
-// KC2: the exact-f32 grid forward on 32-row tiles (NP = 1), 8 waves.  Its operand tile is 64 KiB, so TWO workgroups are resident per CU
-// (four waves per SIMD: the register allocation is bounded to 128 per wave) and one tile's K loop runs under the other's epilogue and
-// barriers.
-template <typename ET, int MS, int FT, int NP, int NW, int MODE, bool LN, int XF> constexpr bool sdfr_mlp_kc2() {
-    return sizeof(ET) == 4 && MS == 32 && FT == 2 && NP == 1 && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0;
+// The kernels with per-tile K compaction (KC / KCJ below): the exact-f32 grid forward on 64-row tiles, plain or ORDER, and the 16-row
+// float32 mask-fed Jacobian.
+template <typename ET, int MS, int FT, int NP, int NW, int MODE, bool LN, int XF> constexpr bool sdfr_mlp_kc() {
+    return sizeof(ET) == 4 && MS == 32 && FT == 2 && NP == 2 && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0;
 }
 template <typename ET, int MS, int FT, int NP, int NW, int MODE, bool LN, int XF> constexpr bool sdfr_mlp_kcj() {
     return sizeof(ET) == 4 && MS == 16 && NP == 1 && NW == 4 && FT == 8 && MODE == 3 && !LN && XF == 0;
 }
 template <typename ET, int MS, int FT, int NP, int NW, int PF, int MODE, int PFB_ = 0, bool LN = false, int XF = 0>
-__global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN, XF>() ? 4 : SDFR_MLP_WPE)) void sdfr_mlp_kernel(const MlpParams P) {
+__global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const MlpParams P) {
     typedef Mma<ET, MS> M;
     typedef typename M::acc_t acc_t;
     typedef typename M::vec_t vec_t;
@@ -272,12 +271,10 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     // Two operand tiles in turn where LDS has the room (half forward modes on tiles of up to 64 rows: 2 x 70 KB): a layer's epilogue writes the
     // NEXT operand into the other tile, so no wave has to wait until every wave has finished READING the current one -- one barrier per layer
     // instead of two.  These tiles are the sphere tracer's passes, each a chain of 8 latency-bound layers (r04, profiles/r04_notes.md section 8).
-#ifndef SDFR_ACT_DBUF
-#define SDFR_ACT_DBUF 1
-#endif
-    constexpr bool DBUF = SDFR_ACT_DBUF && HALF && !JAC && !LN && !SAVE && (2 * KGX * PT * 16 <= 144 * 1024);
-    // (64-row KC kernels, KM below: the zero row of the dense image, 256 bytes right behind the operand tile -- row 512 of kc_slots.h)
-    constexpr int KZ4 = (!HALF && MS == 32 && FT == 2 && NP == 2 && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0) ? SDFR_KCD_ROW_BYTES / 16 : 0;
+    constexpr bool DBUF = HALF && !JAC && !LN && !SAVE && (2 * KGX * PT * 16 <= 144 * 1024);
+    // (KC kernels, described below: the zero row of the dense image, 256 bytes right behind the operand tile -- row 512 of kc_slots.h)
+    constexpr bool KC = sdfr_mlp_kc<ET, MS, FT, NP, NW, MODE, LN, XF>();
+    constexpr int KZ4 = KC ? SDFR_KCD_ROW_BYTES / 16 : 0;
     constexpr int ACT4 = (DBUF ? 2 : 1) * KGX * PT + KZ4;
     // MLDS (r06; the half mask-fed Jacobian on 16x16 products): the ReLU masks of EVERY layer for the tile's rows are fetched once, in the
     // kernel's prologue, and kept in LDS.  Fetched layer by layer in front of each product (r05) the 16 scattered 4-byte gathers per lane sat
@@ -286,39 +283,38 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     constexpr bool MLDS = GMASK && HALF && MS == 16 && HP == 512;
     static_assert(!MLDS || (FT == 4 && NW == 8), "MLDS: a wave owns 64 features = two mask dwords of a row");
     constexpr int MLDS_WORDS = MLDS ? NW * SDFR_MAX_LAYERS * PT * 2 : 0;   // [wave][layer][row] 8 bytes: the wave's 64 mask bits of the row
-    __shared__ float4 lds4[ACT4 + NT / 4 + 32 + (PT + 3) / 4 * 2 + (MASK_WORDS + 3) / 4 + LN_F4 + (MLDS_WORDS + 3) / 4];
+    // offsets in float4: each piece starts where the one before it ends
+    constexpr int O_RED = ACT4, O_ROWS = O_RED + NT / 4, O_GY = O_ROWS + 32, O_SLOTS = O_GY + (PT + 3) / 4, O_MASKS = O_SLOTS + (PT + 3) / 4;
+    constexpr int O_LN = O_MASKS + (MASK_WORDS + 3) / 4, O_MLDS = O_LN + LN_F4, LDS4 = O_MLDS + (MLDS_WORDS + 3) / 4;
+    __shared__ float4 lds4[LDS4];
     vec_t* act = reinterpret_cast<vec_t*>(lds4);                  // [KG][PT] 16-byte vectors: act[k/KV][point][k%KV] -- the operand the products read
     ET* act_e = reinterpret_cast<ET*>(lds4);
     vec_t* actw = DBUF ? act + KGX * PT : act;                    // ... and the one the epilogue writes (the same without the second tile)
     ET* actw_e = reinterpret_cast<ET*>(actw);
-    float* red = reinterpret_cast<float*>(lds4 + ACT4);            // [NT]
-    int* rows = reinterpret_cast<int*>(lds4 + ACT4 + NT / 4);      // [PT] source row of each point (128 ints max)
-    float* gy = reinterpret_cast<float*>(lds4 + ACT4 + NT / 4 + 32);   // [PT] d out / d y_last
-    int* slots = reinterpret_cast<int*>(lds4 + ACT4 + NT / 4 + 32 + (PT + 3) / 4);   // [PT] J slot or -1
-    uint32_t* masks = reinterpret_cast<uint32_t*>(lds4 + ACT4 + NT / 4 + 32 + (PT + 3) / 4 * 2);
-    float* lnred = reinterpret_cast<float*>(lds4 + ACT4 + NT / 4 + 32 + (PT + 3) / 4 * 2 + (MASK_WORDS + 3) / 4);   // [NW][PT]
-    float* lnrstd = lnred + NW * PT;                                                                                   // [layers][PT]
-    uint32_t* mlds = reinterpret_cast<uint32_t*>(lds4 + ACT4 + NT / 4 + 32 + (PT + 3) / 4 * 2 + (MASK_WORDS + 3) / 4 + LN_F4);   // uint2 [NW][layers][PT]
+    float* red = reinterpret_cast<float*>(lds4 + O_RED);          // [NT]
+    int* rows = reinterpret_cast<int*>(lds4 + O_ROWS);            // [PT] source row of each point (128 ints max)
+    float* gy = reinterpret_cast<float*>(lds4 + O_GY);            // [PT] d out / d y_last
+    int* slots = reinterpret_cast<int*>(lds4 + O_SLOTS);          // [PT] J slot or -1
+    uint32_t* masks = reinterpret_cast<uint32_t*>(lds4 + O_MASKS);
+    float* lnred = reinterpret_cast<float*>(lds4 + O_LN);         // [NW][PT]
+    float* lnrstd = lnred + NW * PT;                              // [layers][PT]
+    uint32_t* mlds = reinterpret_cast<uint32_t*>(lds4 + O_MLDS);  // uint2 [NW][layers][PT]
     // MLDS kernels on decoders with at most 8 input columns: a J row is assembled in LDS and written ONCE -- gradients of re-injected input
     // columns (latent_in / xyz_in_all layers) are added here, the first layer's in-gradient joins them at the end.  (r05 zeroed the rows in
     // HBM at the start and atomicAdd-ed both parts: 24 lane-divergent global atomics in the last wave of the re-injecting layer held the
     // other seven waves at the barrier for 4-7 k cycles.)
     __shared__ float jinj[MLDS ? PT * 8 : 1];
     __shared__ int jpfx[JPOOL ? 66 : 1];                          // JPOOL: inclusive prefix of the crops' live tiles (B <= 64), [64] = total
-    // KC (per-tile K compaction of the exact-f32 grid forward): a hidden layer's epilogue keeps only the features that are
-    // non-zero at some point of the tile and writes them to consecutive operand slots, in the order in which the full K chain visits them;
-    // the next product walks that shorter list and gathers its weights from the k-major image Wk.  A skipped term is fma(0, w, acc) == acc
+    // KC (per-tile K compaction of the exact-f32 grid forward): a hidden layer's epilogue lists the features that are
+    // non-zero at some point of the tile at consecutive slots of the k list, in the order in which the full K chain visits them; the next
+    // product walks that shorter list and gathers its weights from the k-major image Wk.  A skipped term is fma(0, w, acc) == acc
     // (up to the sign of a zero accumulator, which no ReLU output keeps), so every output and mask bit is the full chain's.
-    constexpr bool KC2 = sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN, XF>();
-    constexpr bool KC = !HALF && MS == 32 && FT == 2 && (NP == 2 || NP == 1) && NW == 8 && (MODE == 0 || MODE == 1) && !LN && (XF & ~4) == 0;
-    __shared__ int4 kc_list4[KC ? HP / 4 : 1];                    // operand slot -> k * HP (element offset of the k-row in Wk; KM: sdfr_kcd_entry)
+    // The operand of a compacted layer is the dense k-major image of kc_slots.h (feature j = row j, a lane's two points side by side; the
+    // product reads it through the k list); layer 0's input, the full chain and the last hidden layer's operand keep act[k/KV][point][k%KV]
+    __shared__ int4 kc_list4[KC ? HP / 4 : 1];                    // chain slot -> sdfr_kcd_entry of the feature (byte offset of its row in the image)
     __shared__ int4 kc_cnt4[KC ? NW / 4 : 1];                     // surviving features per wave (published by the layer's first barrier)
     int* kc_cnt = reinterpret_cast<int*>(kc_cnt4);
-    // KM: the operand of a compacted layer of the 64-row tiles is the dense k-major image of kc_slots.h (feature j = row j, a lane's two points
-    // side by side; the product reads it through the k list); the 32-row kernel, layer 0's input, the full chain and the last hidden layer's
-    // operand keep act[k/KV][point][k%KV]
-    constexpr bool KM = KC && NP == 2;
-    static_assert(KM == (KZ4 != 0) && (!KM || (KGX * PT * 16 == SDFR_KCD_ZERO_ROW * SDFR_KCD_ROW_BYTES && HP == SDFR_KCD_WK_ROW_FLOATS)),
+    static_assert(!KC || (KGX * PT * 16 == SDFR_KCD_ZERO_ROW * SDFR_KCD_ROW_BYTES && HP == SDFR_KCD_WK_ROW_FLOATS),
                   "kc_slots.h: the dense image is 512 rows of 256 bytes, its zero row right behind it");
     static_assert(!KC || (KT == 8 && KV == 4 && NW == 8), "kc_slots.h: k tiles of 8, vectors of 4, 8 waves");
     // KCJ (K compaction of the band Jacobian's transposed products, 16-row float32 mask-fed kernel; kcj_slots.h): the operand
@@ -329,8 +325,6 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     __shared__ int4 kcj_list4[KCJ ? HP / 4 : 1];                  // [k tile][lane group] the four components' k rows (element offsets in Wkj)
     __shared__ int4 kcj_cnt4[1];                                  // surviving features per wave (published by the barrier behind the product)
     static_assert(!KCJ || (KT == SDFR_KCJ_KT && PT == SDFR_KCJ_PT && KV == 4 && PF == SDFR_KCJ_RING && MW == 1), "kcj_slots.h: 16-row tiles, k tiles of 16, ring of 4");
-    static_assert(!KC2 || (KC && sizeof(lds4) + sizeof(jinj) + sizeof(jpfx) + sizeof(kc_list4) + sizeof(kc_cnt4) <= 80 * 1024),
-                  "KC2: two workgroups per CU, at most 80 KiB of LDS each");
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -656,9 +650,8 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
 #pragma unroll
         for (int u = 0; u < PFB - 1; ++u)
             if (u < nkt) load_b(u, b[u]);
-#ifndef SDFR_STRAIGHT_KLOOP
-#define SDFR_STRAIGHT_KLOOP 1
-#endif
+        // (decided: 0, profiles/r04_notes.md section 10.  The branch is still here because deleting it drops HALF from this closure's captures
+        // and the compiler then allocates the registers of three mlp_jac16 kernels differently: profiles/fwd_retire_notes.md, section 2)
 #ifndef SDFR_UNROLLED_KLOOP
 #define SDFR_UNROLLED_KLOOP 0
 #endif
@@ -686,7 +679,7 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             }
             return;
         }
-        if (SDFR_STRAIGHT_KLOOP && FULL && nkt % PF == 0) {
+        if (FULL && nkt % PF == 0) {
             // The common case (every 512-wide layer): a K loop WITHOUT branches.  Prefetch indices are clamped instead of guarded (the
             // tail re-reads the last tile into ring slots nobody consumes), so the body is one basic block and the compiler's s_waitcnt
             // counts stay exact: with the guarded form below it falls back to vmcnt(0) once per PF tiles -- a wait for loads it has just
@@ -809,25 +802,24 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             else if (nact > 0) gemm_body(Wl, kpad, nact, std::false_type{});
         }
     };
-    // KC product: the operand holds nk compacted slots (a multiple of 2 KT), slot s = k-tile s / KT, lane group (s % KT) / KV, component
+    // KC product: the k list holds nk compacted slots (a multiple of 2 KT), slot s = k-tile s / KT, lane group (s % KT) / KV, component
     // s % KV -- the place where the full chain would have visited its feature.  A lane's weight fragments of BOTH feature tiles are gathered
     // as KV 8-byte pairs of the k-major image (Wk[k][sdfr_wk_row(row)]: 32 lanes of a lane group read 256 contiguous bytes per load; with one
-    // 4-byte gather per feature tile the loop ran 13 % short of its matrix rate); the k list is read from LDS one tile ahead of
-    // the gather it feeds.  Ring of two tiles and clamped prefetch indices, as in gemm_body's branch-free loop (64-row kernels: refilled
-    // component by component, two tiles ahead -- the ring rule of kc_slots.h).  64-row kernels (KM): the
-    // VALUES of slot s wait in the row of the dense image that the slot's k word names (kc_slots.h, sdfr_kcd_*), pads in the zero row.
+    // 4-byte gather per feature tile the loop ran 13 % short of its matrix rate); the k list is read from LDS ahead of the gather it
+    // feeds.  Ring of two tiles and clamped prefetch indices, as in gemm_body's branch-free loop (full-width waves: refilled component by
+    // component, two tiles ahead -- the ring rule of kc_slots.h).  The VALUES of slot s wait in the row of the dense image that the slot's
+    // k word names (kc_slots.h, sdfr_kcd_*), pads in the zero row.
     auto gemm_kc_body = [&](const float* __restrict__ Wl, int nk, int nact, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
         const int nkt = nk / KT;
         if (nkt <= 0) return;
         const float* wp = Wl + fbase + 2 * lp;
-        const vec_t* bptr = act + lg * PT + lp;
         const int4* klp = kc_list4 + lg;
         vec_t a[2][FT], b[2][NP];
         int4 ko[2];
         // (KC kernels have FT = 2; Wk keeps a lane's two rows of one k side by side -- sdfr_wk_row --: ONE 8-byte gather per k and lane instead of one per feature tile)
-        // (KM: a k word is the byte offset of the feature's row in the dense image, sdfr_kcd_entry; 2 x that is its float offset in Wk)
-        constexpr int KE = KM ? SDFR_KCD_WK_ROW_FLOATS / SDFR_KCD_ROW_BYTES : 1;
+        // (a k word is the byte offset of the feature's row in the dense image, sdfr_kcd_entry; 2 x that is its float offset in Wk)
+        constexpr int KE = SDFR_KCD_WK_ROW_FLOATS / SDFR_KCD_ROW_BYTES;
         auto load_a = [&](const int4& k, vec_t* aa) {
             const float2 w0 = *reinterpret_cast<const float2*>(wp + KE * k.x), w1 = *reinterpret_cast<const float2*>(wp + KE * k.y);
             const float2 w2 = *reinterpret_cast<const float2*>(wp + KE * k.z), w3 = *reinterpret_cast<const float2*>(wp + KE * k.w);
@@ -838,21 +830,15 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                 for (int i = 0; i < KV; ++i) aa[FT - 1][i] = (ET)0;
             }
         };
-        auto load_b = [&](int tile, const int4& k, vec_t* bb) {
-            if constexpr (KM) {
-                // dense image: step ks reads the lane's 8 bytes (both point tiles) of the row its k word names -- four 8-byte reads per
-                // tile, each with its own address, two rows of 256 contiguous bytes per read (one per lane group)
-                const int kw[KV] = {k.x, k.y, k.z, k.w};
+        auto load_b = [&](const int4& k, vec_t* bb) {
+            // dense image: step ks reads the lane's 8 bytes (both point tiles) of the row its k word names -- four 8-byte reads per
+            // tile, each with its own address, two rows of 256 contiguous bytes per read (one per lane group)
+            const int kw[KV] = {k.x, k.y, k.z, k.w};
 #pragma unroll
-                for (int ks = 0; ks < KV; ++ks) {
-                    const float2 v = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(act_e) + sdfr_kcd_operand_byte(kw[ks], lp));
-                    bb[0][ks] = v.x;
-                    bb[NP - 1][ks] = v.y;
-                }
-            } else {
-                const vec_t* bp = bptr + tile * (NLG * PT);
-#pragma unroll
-                for (int p = 0; p < NP; ++p) bb[p] = bp[p * MS];
+            for (int ks = 0; ks < KV; ++ks) {
+                const float2 v = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(act_e) + sdfr_kcd_operand_byte(kw[ks], lp));
+                bb[0][ks] = v.x;
+                bb[NP - 1][ks] = v.y;
             }
         };
         auto mma = [&](const vec_t* aa, const vec_t* bb) {
@@ -865,8 +851,11 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                         for (int p = 0; p < NP; ++p) acc[f][p] = M::step(aa[f], bb[p], acc[f][p], ks);
                     }
         };
-        if constexpr (KM && FULL) {
-            // 64-row kernels, full-width waves: the ring rule of kc_slots.h (sdfr_kc_ring_*).  A fragment stage is refilled component by
+        // (KC is implied: only KC kernels instantiate this body.  Naming it makes the closure capture it, as it captured the predicate of
+        // the 32-row geometry that once shared this loop; without it the compiler allocates the two kernels' registers differently --
+        // profiles/fwd_retire_notes.md, section 2)
+        if constexpr (KC && FULL) {
+            // full-width waves: the ring rule of kc_slots.h (sdfr_kc_ring_*).  A fragment stage is refilled component by
             // component -- the 8-byte gather of (tile t + 2, component ks) goes out right behind the four matrix instructions that read
             // component ks of tile t -- so a gather that misses L2 has seven groups of four matrix instructions to land instead of the four
             // the whole-tile ring gave it, in the same registers.  The layer's first gathers go out before the accumulators are zeroed.
@@ -926,20 +915,21 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             }
             return;
         }
+        // waves that are not full width (a layer narrower than HP): whole tiles in two stages, the k list one tile ahead
         const int last = nkt - 1;
         ko[0] = klp[0];
         load_a(ko[0], a[0]);
-        load_b(0, ko[0], b[0]);
+        load_b(ko[0], b[0]);
         ko[1] = klp[min(1, last) * NLG];
         for (int t = 0; t < nkt; t += 2) {
             load_a(ko[1], a[1]);
-            load_b(min(t + 1, last), ko[1], b[1]);
+            load_b(ko[1], b[1]);
             ko[0] = klp[min(t + 2, last) * NLG];
             __builtin_amdgcn_sched_barrier(0);
             mma(a[0], b[0]);
             __builtin_amdgcn_sched_barrier(0);
             load_a(ko[0], a[0]);
-            load_b(min(t + 2, last), ko[0], b[0]);
+            load_b(ko[0], b[0]);
             ko[1] = klp[min(t + 3, last) * NLG];
             __builtin_amdgcn_sched_barrier(0);
             mma(a[1], b[1]);
@@ -950,8 +940,8 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         int nact = (rows_active - fbase + MS - 1) / MS;
         nact = nact < 0 ? 0 : (nact > FT ? FT : nact);
         nact = __builtin_amdgcn_readfirstlane(nact);
-        // (64-row kernels: the body zeroes the accumulators itself, behind its first gathers)
-        if (!KM || nact != FT || nk < KT) {
+        // (full-width waves: the body zeroes the accumulators itself, behind its first gathers)
+        if (nact != FT || nk < KT) {
 #pragma unroll
             for (int f = 0; f < FT; ++f)
 #pragma unroll
@@ -1098,7 +1088,7 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
     int* t_more = reinterpret_cast<int*>(gy);           // gy is unused by forward modes
     const bool kc_on = KC && P.kcompact && P.Wk;
     int kc_n = 0;                                       // KC: compacted K extent of the operand the next product reads
-    if constexpr (KM) {
+    if constexpr (KC) {
         // the zero row of the dense image, written once per workgroup (layer 0's barriers lie between this store and its first reader)
         if (kc_on && tid < KZ4) lds4[KGX * PT + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -1139,7 +1129,7 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         // The survivor vote costs no ballot per feature: a ReLU output is non-zero exactly where its mask bit is set, so the lane's mask
         // words already say which of its 32 registers are alive at one of its points; ONE OR-reduction of that word over each lane group
         // (4 DPP steps inside the rows of 16 lanes, then the four row heads) gives the wave's two survivor words kc_w[g], bit q.  Only the
-        // wave and layer that re-inject input columns force those bits.  (64-row tiles; the 32-row kernel votes by ballot.)
+        // wave and layer that re-inject input columns force those bits.
         uint32_t kc_w[2] = {0u, 0u};
         auto kc_values = [&](auto inj_tag) {
             constexpr bool INJ = decltype(inj_tag)::value;
@@ -1155,7 +1145,6 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                         const bool inj = INJ && j0 + i >= inj_lo && j0 + i < inj_hi;
                         const int q = (f * RG + rg) * 4 + i;
                         if (INJ) injw |= (inj ? 1u : 0u) << q;
-                        bool nz = inj;
 #pragma unroll
                         for (int p = 0; p < NP; ++p) {
                             const float x = acc[f][p][rg * 4 + i] + f4c(b4, i);
@@ -1165,16 +1154,9 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                             mw[bit >> 5] |= (pos ? 1u : 0u) << (bit & 31);
                             if (INJ && inj) v = P.inputs[(int64_t)rows[p * MS + lp] * NI + Ln.inj_off + (j0 + i - inj_lo)];
                             acc[f][p][rg * 4 + i] = v;
-                            if constexpr (NP == 1) nz = nz || v != 0.f;
-                        }
-                        if constexpr (NP == 1) {              // 32-row tiles keep the ballot per feature (the word vote costs them 26 more spills)
-                            const uint64_t bal = __ballot(nz);
-                            kc_w[0] |= (uint32_t)((uint32_t)bal != 0u) << q;
-                            kc_w[1] |= (uint32_t)((bal >> 32) != 0ull) << q;
                         }
                     }
                 }
-            if constexpr (NP == 1) return;
             // bit q = (f RG + rg) 4 + i: register q's feature is alive at one of this lane's two points
             uint32_t nzw = ((mw[0] | (mw[0] >> 16)) & 0xffffu) | ((mw[MW - 1] | (mw[MW - 1] >> 16)) << 16);
             if (INJ) nzw |= injw;
@@ -1201,11 +1183,10 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             if (lnl) ln_forward(l, L.out_dim);          // acc already holds gamma * x_hat + beta (bias included)
         }
         // KC, after the barrier: the survivors of the waves in front of this one give its first chain position; survivor number `pos` of
-        // the layer goes to operand slot (pos / KT) KT + (pos % 2) KV + (pos % KT) / 2 -- k tile, lane group, component of the full chain's
-        // order -- and the k list gets its weight row.  The last wave pads the list to a multiple of 2 KT with zero activations (k = 0).
-        // That is the image of the 32-row kernel.  The 64-row kernels (KM) keep the k list's places and order and do NOT compact the values:
-        // every feature goes to its own row of 64 dwords (the dense image of kc_slots.h), the k list names rows, and wave 0 pads the list
-        // with the zero row.  The product needs the list of survivors only -- it walks it anyway for its weights.
+        // the layer goes to slot (pos / KT) KT + (pos % 2) KV + (pos % KT) / 2 of the k list -- k tile, lane group, component of the full
+        // chain's order.  The VALUES are not compacted: every feature goes to its own row of 64 dwords (the dense image of kc_slots.h), the
+        // k list names rows, and wave 0 pads the list to a multiple of 2 KT with the zero row.  The product needs the list of survivors
+        // only -- it walks it anyway for its weights.
         auto kc_store = [&]() {
             int off = 0, tot = 0;
             {
@@ -1219,76 +1200,41 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
             }
             off = __builtin_amdgcn_readfirstlane(off);
             tot = __builtin_amdgcn_readfirstlane(tot);
-            if constexpr (KM) {
-                // dense image (kc_slots.h, sdfr_kcd_*): feature j owns row j, a lane's two points of register q's feature are neighbours
-                // there.  32 unconditional 8-byte stores from ONE address register (the lane's part, made opaque so that each register's row
-                // stays the store's immediate offset); dead features store their zeros, and no survivor word is looked at.  16 lanes lie on
-                // 32 consecutive dwords, lane group 1 writes the row 4 further.
-                {
-                    int dl = sdfr_kcm_lane_dword(sdfr_kcd_row(fbase + sdfr_kcd_row_lane(0, lg)), lp);
-                    asm volatile("" : "+v"(dl));
+            // dense image (kc_slots.h, sdfr_kcd_*): feature j owns row j, a lane's two points of register q's feature are neighbours
+            // there.  32 unconditional 8-byte stores from ONE address register (the lane's part, made opaque so that each register's row
+            // stays the store's immediate offset); dead features store their zeros, and no survivor word is looked at.  16 lanes lie on
+            // 32 consecutive dwords, lane group 1 writes the row 4 further.
+            {
+                int dl = sdfr_kcm_lane_dword(sdfr_kcd_row(fbase + sdfr_kcd_row_lane(0, lg)), lp);
+                asm volatile("" : "+v"(dl));
 #pragma unroll
-                    for (int f = 0; f < FT; ++f)
+                for (int f = 0; f < FT; ++f)
 #pragma unroll
-                        for (int r = 0; r < RG * 4; ++r)
-                            *reinterpret_cast<float2*>(act_e + dl + sdfr_kcm_lane_dword(sdfr_kcd_row_reg(f * RG * 4 + r), 0)) =
-                                make_float2(acc[f][0][r], acc[f][NP - 1][r]);
-                }
-                {   // k list: lane (g, q) enters the row of register q's feature, lane group g, at the place the chain order gives it
-                    const int q = lp;
-                    if ((kc_w[lg] >> q) & 1u) {
-                        const int j = fbase + sdfr_kcd_feature(0, q, lg);
-                        reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(off + sdfr_kc_rank(kc_w[0], kc_w[1], q, lg))] = sdfr_kcd_entry(j);
-                    }
-                }
-                // padding: the k entries [tot, padded) name the zero row (one predicated store of wave 0); nothing is stored to the image
-                const int padded = sdfr_kc_padded(tot);
-                if (sdfr_kcm_pads(wave)) {
-                    if (lane < padded - tot) reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(tot + lane)] = sdfr_kcd_pad_entry();
-                }
-                kc_n = padded;
-                return;
+                    for (int r = 0; r < RG * 4; ++r)
+                        *reinterpret_cast<float2*>(act_e + dl + sdfr_kcm_lane_dword(sdfr_kcd_row_reg(f * RG * 4 + r), 0)) =
+                            make_float2(acc[f][0][r], acc[f][NP - 1][r]);
             }
-#pragma unroll
-            for (int f = 0; f < FT; ++f)
-#pragma unroll
-                for (int rg = 0; rg < RG; ++rg)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int q = (f * RG + rg) * 4 + i;
-                        // (wave-uniform: the survivors in front of register q, and whether lane group 0's feature goes first)
-                        const int below = sdfr_kc_rank(kc_w[0], kc_w[1], q, 0);
-                        const bool b0 = (kc_w[0] >> q) & 1u, b1 = (kc_w[1] >> q) & 1u;
-                        if (lg ? b1 : b0) {
-                            const int s = sdfr_kc_slot(off + below + ((lg && b0) ? 1 : 0));
-#pragma unroll
-                            for (int p = 0; p < NP; ++p) act_e[((s / KV) * PT + p * MS + lp) * KV + (s % KV)] = acc[f][p][rg * 4 + i];
-                        }
-                    }
-            {   // k list: lane (g, q) enters the feature of register q, lane group g
+            {   // k list: lane (g, q) enters the row of register q's feature, lane group g, at the place the chain order gives it
                 const int q = lp;
                 if ((kc_w[lg] >> q) & 1u) {
-                    const int j = fbase + (q >> 4) * MS + ((q >> 2) & 3) * (4 * NLG) + 4 * lg + (q & 3);
-                    reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(off + sdfr_kc_rank(kc_w[0], kc_w[1], q, lg))] = j * HP;
+                    const int j = fbase + sdfr_kcd_feature(0, q, lg);
+                    reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(off + sdfr_kc_rank(kc_w[0], kc_w[1], q, lg))] = sdfr_kcd_entry(j);
                 }
             }
+            // padding: the k entries [tot, padded) name the zero row (one predicated store of wave 0); nothing is stored to the image
             const int padded = sdfr_kc_padded(tot);
-            if (sdfr_kc_pads(wave, NW)) {
-                for (int e = 0; e < padded - tot; ++e) {
-                    const int s = sdfr_kc_slot(tot + e);
-                    if (lane < PT) act_e[((s / KV) * PT + lane) * KV + (s % KV)] = 0.f;       // (lane = point)
-                    if (lane == e) reinterpret_cast<int*>(kc_list4)[s] = 0;
-                }
+            if (sdfr_kcm_pads(wave)) {
+                if (lane < padded - tot) reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(tot + lane)] = sdfr_kcd_pad_entry();
             }
             kc_n = padded;
         };
         auto epilogue = [&](auto inj_tag) {
             constexpr bool INJ = decltype(inj_tag)::value;
-            // 64-row KC kernels: ONE address register per layer for the sixteen 16-byte stores -- the lane's part of the address, made opaque
+            // KC kernels: ONE address register per layer for the sixteen 16-byte stores -- the lane's part of the address, made opaque
             // so that the rest of each address stays a constant the store carries as its offset.  Left to itself the compiler builds the sixteen
             // addresses with ORs once in the kernel's prologue and keeps them across every product loop (ten of them in scratch).
             int elane = ((fbase / KV + lg) * PT + lp) * KV;
-            if constexpr (KM) asm volatile("" : "+v"(elane));
+            if constexpr (KC) asm volatile("" : "+v"(elane));
 #pragma unroll
             for (int f = 0; f < FT; ++f)
 #pragma unroll
@@ -1317,7 +1263,7 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                                     if (j0 + i >= inj_lo && j0 + i < inj_hi) v[i] = src[j0 + i];
                             }
                         }
-                        if constexpr (KM) store4(actw_e + elane + (((f * MS + rg * 4 * NLG) / KV) * PT + p * MS) * KV, v);
+                        if constexpr (KC) store4(actw_e + elane + (((f * MS + rg * 4 * NLG) / KV) * PT + p * MS) * KV, v);
                         else store4(actw_e + ((j0 / KV) * PT + pt) * KV + (j0 % KV), v);
                     }
                 }
@@ -1359,15 +1305,9 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
                         t[0] = lo[0]; t[1] = lo[1]; t[2] = hi[0]; t[3] = hi[1];
                         *reinterpret_cast<h16x4*>(actw_e + ((j0 / KV) * PT + pt) * KV + (j0 % KV)) = t;
                     }
-#ifdef SDFR_EPI_FENCE
-                    __builtin_amdgcn_sched_barrier(0);         // (A/B: one accumulator tile's reads at a time -- 512-register geometries)
-#endif
                 }
         };
-#ifndef SDFR_H_FAST_EPI
-#define SDFR_H_FAST_EPI 1
-#endif
-        if constexpr (SDFR_H_FAST_EPI && HALF && !LN && !JAC) {
+        if constexpr (HALF && !LN && !JAC) {
 #ifdef SDFR_ABL_NOEPI
             if (acc[0][0][0] == 12345.f) epilogue_half_fast();  // ablation (timing only, wrong results): barriers stay, the epilogue's work goes
 #else
@@ -1439,10 +1379,9 @@ __global__ __launch_bounds__(64 * NW, (sdfr_mlp_kc2<ET, MS, FT, NP, NW, MODE, LN
         // k slices of the last linear's dot product.  Half operands: ONE partition (4 slices of 128 k, summed in order) for every tile
         // geometry, so that a row's value has the same bits whether a 128-, 64- or 16-row tile evaluated it (r04: the sphere tracer's
         // march picks the tile size by the device-side row count, and a crop must march the same alone and in a batch); float32: as many
-        // slices as the workgroup has threads per point (unchanged bits) -- except KC2: the grid forward's partition stays the 64-row tile's,
-        // 8 slices of 64 k summed in order, so that a row has the same bits under both tile sizes; the threads beyond 8 PT idle here.
-        constexpr int SL = HALF ? (NT / PT < 4 ? NT / PT : 4) : (KC2 ? 8 : NT / PT);       // (fewer than 4 threads per point: A/B geometries only)
-        static_assert(!KC || (SL == 8 && KG / SL * KV == 64), "exact-f32 grid forward: last linear in 8 slices of 64 k, whatever the tile");
+        // slices as the workgroup has threads per point (unchanged bits; the exact-f32 grid forward: 8 slices of 64 k summed in order).
+        constexpr int SL = HALF ? (NT / PT < 4 ? NT / PT : 4) : NT / PT;       // (fewer than 4 threads per point: A/B geometries only)
+        static_assert(!KC || (SL == 8 && KG / SL * KV == 64), "exact-f32 grid forward: last linear in 8 slices of 64 k");
         static_assert(SL * PT <= NT, "last linear: one thread per (slice, point)");
         constexpr int KGS = KG / SL;
         const int sl = tid / PT, pt = tid - sl * PT;

@@ -5,7 +5,6 @@ must match one of the 2^k reference Jacobians), each within c u mass of that ele
 emulations (tests/test_decoder_refs_cpu.py), not from the kernels; profiles/decoder_tests_notes.md has the figures.  Every path prints a
 line starting DECODERTEST with its largest ratio observed / allowed."""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -56,7 +55,7 @@ def fwd_tile(net, arith):
     """rows per workgroup of the forward that saves masks"""
     if arith == "f16":
         return 128
-    return int(os.environ.get("SDFR_FWD_TILE", "64")) if (arith == "f32" and net.hp == 512) else 64
+    return 64
 
 
 def check_rows_beyond(ws, n, tile, n_layers, hp):
@@ -134,11 +133,10 @@ def test_forward_f32_every_row(name):
     _forward_sizes(name, "f32")
 
 
-@pytest.mark.parametrize("tile,compact", [("32", "1"), ("32", "0"), ("64", "0")])
+@pytest.mark.parametrize("tile,compact", [("64", "0")])
 @pytest.mark.parametrize("name", C.NAMES_512)
 def test_forward_f32_every_row_other_tiles(name, tile, compact, monkeypatch):
-    """the exact-f32 grid forward on 32-row tiles (two workgroups per CU) and with the full K chain instead of the per-tile K compaction"""
-    monkeypatch.setenv("SDFR_FWD_TILE", tile)
+    """the exact-f32 grid forward with the full K chain instead of the per-tile K compaction"""
     monkeypatch.setenv("SDFR_FWD_COMPACT", compact)
     _forward_sizes(name, "f32", " tile=%s compact=%s" % (tile, compact))
 

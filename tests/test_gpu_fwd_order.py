@@ -1,10 +1,10 @@
 """GPU tests of the ordered exact-f32 grid forward (sdfr_mlp_forward_ordered; mlp_kernel.h ORDER): with the rows of a tile chosen
 by sdfr_grid_tile_order -- 4x4x4 blocks of the grid instead of 64 consecutive rows -- every sdf value and every saved ReLU mask word of every
-row of the launch must be bit for bit what the plain launch writes: both tile sizes, per-tile K compaction on and off, with and without a mask
-buffer.  One BatchRenderer step and a captured BatchRefiner run must not depend on SDFR_FWD_ORDER, and an index outside the order's range
+row of the launch must be bit for bit what the plain launch writes: per-tile K compaction on and off, with and without a mask buffer.  One BatchRenderer step and a captured BatchRefiner run must not depend on SDFR_FWD_ORDER, and an index outside the order's range
 must cost its slot's row and nothing else.
 
-Mask words are compared for the rows of the launch (tests/test_gpu_fwd32_tiles.py: the padding behind the last row is nobody's)."""
+Mask words are compared for the rows of the launch.  The mask buffer is padded to whole 128-row blocks; what a launch leaves in the padding
+rows behind its last row (a partial tile writes the bits of mirrored rows up to the end of the tile) is nobody's and nothing reads it."""
 import numpy as np
 import pytest
 import torch
@@ -12,7 +12,7 @@ import torch
 import sdflabel_amd
 from sdflabel_amd import _lib
 from sdflabel_amd.fixtures import ASSET, ASSET_ELLIPSOID, K_for
-from tests.test_gpu_fwd32_tiles import grid_inputs, mask_rows
+from tests.test_gpu_kcompact import grid_inputs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -35,14 +35,19 @@ def tile_order(D):
     return torch.from_numpy(o)
 
 
-def launch(dec, inputs, order, monkeypatch, tile="64", compact=True, masks=True):
+def mask_rows(mw, n, n_layers=8, hp32=16):
+    """the mask words of rows 0 .. n-1 (layout v2: [block of 128 rows][layer][row in block][HP / 32 dwords]) as [layer][row][dword]"""
+    v = mw.view(-1, n_layers, 128, hp32).permute(1, 0, 2, 3).reshape(n_layers, -1, hp32)
+    return v[:, :n]
+
+
+def launch(dec, inputs, order, monkeypatch, compact=True, masks=True):
     """order None: the plain launch.  sdf starts as NaN and the mask words as zero, so a row never written shows."""
     L = _lib.lib()
     h = dec.handle(torch.device(DEV)).h
     n = inputs.shape[0]
     sdf = torch.full((n,), float("nan"), device=DEV)
     mw = torch.zeros(int(L.sdfr_decoder_mask_words(h, n)), dtype=torch.int32, device=DEV) if masks else None
-    monkeypatch.setenv("SDFR_FWD_TILE", tile)
     monkeypatch.setenv("SDFR_FWD_COMPACT", "1" if compact else "0")
     if order is None:
         _lib.check(L.sdfr_mlp_forward(h, _lib.ptr(inputs), n, _lib.ptr(sdf), _lib.ptr(mw), _lib.stream_ptr()), "sdfr_mlp_forward")
@@ -54,15 +59,14 @@ def launch(dec, inputs, order, monkeypatch, tile="64", compact=True, masks=True)
 
 
 def assert_ordered_equals_plain(dec, inputs, order, monkeypatch):
-    ref_s, ref_m = launch(dec, inputs, None, monkeypatch)               # the reference: one plain launch, shared by the eight variants
+    ref_s, ref_m = launch(dec, inputs, None, monkeypatch)               # the reference: one plain launch, shared by the four variants
     assert torch.isfinite(ref_s).all() and ref_m.shape[1] == inputs.shape[0]
-    for tile in ("64", "32"):
-        for compact in (True, False):
-            for masks in (True, False):
-                s, m = launch(dec, inputs, order, monkeypatch, tile, compact, masks)
-                assert torch.equal(ref_s.view(torch.int32), s.view(torch.int32)), (tile, compact, masks)
-                if masks:
-                    assert torch.equal(ref_m, m), (tile, compact, masks)
+    for compact in (True, False):
+        for masks in (True, False):
+            s, m = launch(dec, inputs, order, monkeypatch, compact, masks)
+            assert torch.equal(ref_s.view(torch.int32), s.view(torch.int32)), (compact, masks)
+            if masks:
+                assert torch.equal(ref_m, m), (compact, masks)
 
 
 @pytest.mark.parametrize("D,crops", [(4, 1), (5, 1), (6, 1), (8, 1), (5, 2)])
@@ -80,8 +84,7 @@ def test_headline_grid_bitwise(asset, monkeypatch):
     assert_ordered_equals_plain(_decoder(asset), inp, tile_order(40).to(DEV), monkeypatch)
 
 
-@pytest.mark.parametrize("tile", ["64", "32"])
-def test_index_out_of_range_costs_its_own_row_only(dec, tile, monkeypatch):
+def test_index_out_of_range_costs_its_own_row_only(dec, monkeypatch):
     """entries G and -1 planted in the order: the launch finishes, the two rows those slots should have named keep the prefill (NaN, zero mask
     words), every other row has the plain launch's bits"""
     D = 6
@@ -91,7 +94,7 @@ def test_index_out_of_range_costs_its_own_row_only(dec, tile, monkeypatch):
     lost = [int(order[70]), int(order[215])]                         # (slot 215: the last one of a crop, in a partial tile of crop 0 / 1)
     order[70], order[215] = G, -1
     ref_s, ref_m = launch(dec, inp, None, monkeypatch)
-    s, m = launch(dec, inp, order.to(DEV), monkeypatch, tile)
+    s, m = launch(dec, inp, order.to(DEV), monkeypatch)
     gone = torch.zeros(2 * G, dtype=torch.bool, device=DEV)
     for c in range(2):
         for r in lost:
