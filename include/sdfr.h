@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 415        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 416        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -45,7 +45,9 @@ extern "C" {
  * sdfr_lidar_normals and sdfr_depth_map_masked; 409: the training-crop augmentation, sdfr_augment; 410: the grid forward with the caller's tile order,
  * sdfr_grid_tile_order and sdfr_mlp_forward_ordered; 411: triangle meshes, sdfr_mesh_*; 412: verification of
  * refined labels, sdfr_mesh_raster and sdfr_verify_*; 413: the export of training crops, sdfr_crop_*; 414: synthetic
- * bootstrap crops, sdfr_synth_*; 415: signed distances to meshes and surface samples, sdfr_mesh_sdf* and sdfr_mesh_surface_*).  A caller built
+ * bootstrap crops, sdfr_synth_*; 415: signed distances to meshes and surface samples, sdfr_mesh_sdf* and sdfr_mesh_surface_*; 416: the
+ * grid forward's launch order from the last pass, sdfr_mlp_balance_* and sdfr_mlp_forward_balanced, and the per-workgroup tile trace of trace
+ * builds, sdfr_debug_set_tile_trace).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -102,7 +104,26 @@ int sdfr_grid_tile_order(int D, int32_t* out);
  * order_rows rows each; order_rows need not be a multiple of the tile).  Float32 decoders of padded width 512 without LayerNorm. */
 int sdfr_mlp_forward_ordered(const sdfr_decoder* dec, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, const int32_t* order,
                              int64_t order_rows, void* stream);
-/* the same with float16 operands on the matrix cores (weights and hidden activations rounded to half, float32 accumulation, bias,
+/* sdfr_mlp_forward_ordered with the launch order of the 64-entry chunks of `order` taken from the last pass (SDFR_VERSION 416).  Since the
+ * K compaction a tile's time follows the K extent its products walk, and the one-crop launch is under four tiles per CU: launched in
+ * the static order the heavy late tiles make a tail.  Every tile of a balanced launch adds that K extent (an integer) to its chunk's word of
+ * `state`, and a small kernel behind the launch ranks the full chunks by (cost descending, static index ascending) and writes the
+ * order of the NEXT call; a partial last chunk keeps the last place.  sdf and mask_ws receive what sdfr_mlp_forward writes, bit for bit,
+ * whatever the state holds: chunks stay whole, and the next order is always written from the state's own copy of the static order.
+ *   state   DEVICE memory of sdfr_mlp_balance_bytes(order_rows) bytes, 4-byte aligned, int32 words, T = (order_rows + 63) / 64:
+ *           [0, T) costs added since the last ranking; [T, 2 T) the costs the last ranking read; [2 T, 3 T) the chunk of the static order at each
+ *           place of the next launch; 4 control words; order_rows words, the order the next call launches with; order_rows words, the
+ *           static order.  One state per order and stream of calls.
+ *   sdfr_mlp_balance_init   order: DEVICE int32 [order_rows]; writes it to both order fields and zeroes the costs (one kernel); the state
+ *           must be memory of the current device (checked).
+ *   sdfr_mlp_forward_balanced   arguments and checks of sdfr_mlp_forward_ordered.  Two launches, no host read, no synchronisation, no
+ *           pointer that changes from call to call: a captured graph replays it.  Orders of more than 4096 chunks (tens of rounds of tiles:
+ *           no tail) are launched in the static order and not ranked. */
+int64_t sdfr_mlp_balance_bytes(int64_t order_rows);
+int sdfr_mlp_balance_init(void* state, const int32_t* order, int64_t order_rows, void* stream);
+int sdfr_mlp_forward_balanced(const sdfr_decoder* dec, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, void* state,
+                              int64_t order_rows, void* stream);
+/* sdfr_mlp_forward with float16 operands on the matrix cores (weights and hidden activations rounded to half, float32 accumulation, bias,
  * ReLU and tanh) -- the decoder precision of the reference's default config (configs/config_refine.ini:19); inputs/outputs stay float32. */
 int sdfr_mlp_forward_f16(const sdfr_decoder* dec, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, void* stream);
 
@@ -1095,6 +1116,11 @@ int sdfr_mesh_surface_points(const float* vertices, int64_t V, const int32_t* fa
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (8 waves * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */
 int sdfr_debug_set_trace(void* device_buffer);
+/* Debug only: sdfr_mlp_forward and sdfr_mlp_forward_ordered of a library built with -DSDFR_MLP_TRACE write one record of 6 uint64 per
+ * workgroup into this device buffer of `tiles` records: shader clock at the workgroup's start, 100 MHz constant clock at its start, the same
+ * two at its end (behind the tile's sdf store), XCC_ID << 32 | HW_ID of the CU it ran on, blockIdx.x (see tools/tile_gantt.py).  Workgroups
+ * beyond `tiles` write nothing; NULL or tiles <= 0 disables it.  Production builds ignore it. */
+int sdfr_debug_set_tile_trace(void* device_buffer, int64_t tiles);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDFR_LIB") or os.path.join(_HERE, "lib", "libsdfr_hip.so")     # SDFR_LIB: A/B builds (tools/ab_build.sh)
 
-ABI_VERSION = 415          # include/sdfr.h SDFR_VERSION
+ABI_VERSION = 416          # include/sdfr.h SDFR_VERSION
 _lib = None
 
 # name -> (restype, argtypes); mirrors include/sdfr.h one to one
@@ -18,6 +18,7 @@ _PROTOS = {
     "sdfr_build_flags": (c_int, []),
     "sdfr_last_error": (c_char_p, []),
     "sdfr_debug_set_trace": (c_int, [c_void_p]),
+    "sdfr_debug_set_tile_trace": (c_int, [c_void_p, c_int64]),
     "sdfr_mlp_forward_counted": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     "sdfr_trace_setup": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -77,6 +78,9 @@ _PROTOS = {
     "sdfr_mlp_forward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sdfr_grid_tile_order": (c_int, [c_int, c_void_p]),
     "sdfr_mlp_forward_ordered": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sdfr_mlp_balance_bytes": (c_int64, [c_int64]),
+    "sdfr_mlp_balance_init": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "sdfr_mlp_forward_balanced": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sdfr_mlp_forward_f16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sdfr_mlp_forward_f16_counted": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdfr_mlp_forward_split": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
@@ -314,7 +318,7 @@ _NO_GUARD = _NoGuard()
 
 
 TRAFFIC_SOURCES = {          # the csrc files that define the kernels a profiles/traffic_*.json file was measured on (bench.py, tools/summarize_profile.py)
-    "traffic_mlp_forward.json": ("mlp_kernel.h", "kc_slots.h", "mlp.hip", "mlp_fwd32.hip"),
+    "traffic_mlp_forward.json": ("mlp_kernel.h", "kc_slots.h", "tile_balance.h", "mlp.hip", "mlp_fwd32.hip", "mlp_balance.hip"),
     "traffic_splat.json": ("splat.hip", "splat_bbox.h"),
     "traffic_sphere_step.json": ("trace.hip",),
 }

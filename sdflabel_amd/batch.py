@@ -75,6 +75,15 @@ class BatchRenderer:
             order = torch.empty(self.G, dtype=torch.int32)
             ck(_lib.lib().sdfr_grid_tile_order(int(density), P(order)), "sdfr_grid_tile_order")
             self.fwd_order = order.to(dev)
+            # The launch order of those tiles follows the last pass (sdfr_mlp_forward_balanced, csrc/tile_balance.h): a tile's time goes with
+            # the K extent its compacted products walk, the one-crop launch is 3.9 tiles per CU, so each forward reports its tiles' costs into
+            # this state and a small kernel behind it puts the heaviest first for the next call.  The first call runs the static order;
+            # set_params / set_crops leave the state alone (a stale prior costs time at worst, never a bit).  SDFR_FWD_BALANCE=0, read at
+            # every launch, selects the static order.
+            lib = _lib.lib()
+            self.fwd_balance = torch.empty(int(lib.sdfr_mlp_balance_bytes(self.G)) // 4, dtype=torch.int32, device=dev)
+            with _lib.guard(dev):                           # (a launch: the renderer's device must be current, as in forward())
+                ck(lib.sdfr_mlp_balance_init(P(self.fwd_balance), P(self.fwd_order), self.G, _lib.stream_ptr()), "sdfr_mlp_balance_init")
         self.cap = int(cap) if cap is not None else max(256, self.G // 8)       # surfel capacity per crop
         self._init_extents(K, max_pixels, max_side)
         self._alloc_common()
@@ -414,7 +423,10 @@ class BatchRenderer:
         """the mode's kernel over the whole grid (values + ReLU masks) -> band -> mask-fed Jacobian of the band rows"""
         B, G, cap = self.B, self.G, self.cap
         fwd = L.sdfr_mlp_forward_f16 if self.f16 else (L.sdfr_mlp_forward_split if self.split else L.sdfr_mlp_forward)
-        if self.fwd_order is not None and os.environ.get("SDFR_FWD_ORDER", "1") != "0":
+        if self.fwd_order is not None and os.environ.get("SDFR_FWD_ORDER", "1") != "0" and os.environ.get("SDFR_FWD_BALANCE", "1") != "0":
+            ck(L.sdfr_mlp_forward_balanced(self.handle.h, P(self.inputs), B * G, P(self.sdf), P(self.mask_ws), P(self.fwd_balance), G, st),
+               "sdfr_mlp_forward_balanced")
+        elif self.fwd_order is not None and os.environ.get("SDFR_FWD_ORDER", "1") != "0":
             ck(L.sdfr_mlp_forward_ordered(self.handle.h, P(self.inputs), B * G, P(self.sdf), P(self.mask_ws), P(self.fwd_order), G, st),
                "sdfr_mlp_forward_ordered")
         else:

@@ -33,6 +33,7 @@ $HIPCC $COMMON $SDFR_SPLIT_DEFS -c "$HERE/mlp_split.hip" -o "$HERE/obj/mlp_split
 $HIPCC $COMMON $SDFR_J16_DEFS -c "$HERE/mlp_jac16.hip" -o "$HERE/obj/mlp_jac16.o" &
 $HIPCC $COMMON $SDFR_JAC_DEFS -c "$HERE/mlp_jac.hip"   -o "$HERE/obj/mlp_jac.o" &
 $HIPCC $COMMON -c "$HERE/mlp_persist.hip" -o "$HERE/obj/mlp_persist.o" &
+$HIPCC $COMMON -c "$HERE/mlp_balance.hip" -o "$HERE/obj/mlp_balance.o" &
 $HIPCC $COMMON -c "$HERE/mlp_small.hip" -o "$HERE/obj/mlp_small.o" &
 $HIPCC $COMMON -c "$HERE/mlp_ln.hip"    -o "$HERE/obj/mlp_ln.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/surface.hip" -o "$HERE/obj/surface.o" &
@@ -56,5 +57,5 @@ $HIPCC $COMMON -ffp-contract=off -c "$HERE/crops.hip" -o "$HERE/obj/crops.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/synth.hip" -o "$HERE/obj/synth.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/mesh_sdf.hip" -o "$HERE/obj/mesh_sdf.o" &
 wait
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/${SDFR_LIBNAME:-libsdfr_hip.so}" "$HERE"/obj/{common,mlp,mlp_fwd32,mlp_fwd16,mlp_split,mlp_jac,mlp_jac16,mlp_persist,mlp_small,mlp_ln,surface,project,splat,params,losses,trace,pose,box_iou,detection_eval,frame,ingest,augment,normals,css_head,css_train,mesh,verify,crops,synth,mesh_sdf}.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/${SDFR_LIBNAME:-libsdfr_hip.so}" "$HERE"/obj/{common,mlp,mlp_fwd32,mlp_fwd16,mlp_split,mlp_jac,mlp_jac16,mlp_persist,mlp_balance,mlp_small,mlp_ln,surface,project,splat,params,losses,trace,pose,box_iou,detection_eval,frame,ingest,augment,normals,css_head,css_train,mesh,verify,crops,synth,mesh_sdf}.o
 echo "built $OUT/${SDFR_LIBNAME:-libsdfr_hip.so}"

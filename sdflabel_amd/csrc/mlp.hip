@@ -175,6 +175,15 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
 // workgroup 0 (tools/cycle_trace.py); NULL (the default) disables it.  Not part of the renderer path.
 static unsigned long long* g_trace = nullptr;
 extern "C" int sdfr_debug_set_trace(void* device_buffer) { g_trace = (unsigned long long*)device_buffer; return SDFR_OK; }
+// Debug: device buffer of `tiles` records of SDFR_TILE_TRACE_WORDS uint64 (mlp_kernel.h) that sdfr_mlp_forward and sdfr_mlp_forward_ordered of
+// a library built with -DSDFR_MLP_TRACE fill, one record per workgroup (tools/tile_gantt.py); NULL or tiles <= 0 disables it.
+static unsigned long long* g_tile_trace = nullptr;
+static int64_t g_tile_trace_cap = 0;
+extern "C" int sdfr_debug_set_tile_trace(void* device_buffer, int64_t tiles) {
+    g_tile_trace = tiles > 0 ? (unsigned long long*)device_buffer : nullptr;
+    g_tile_trace_cap = g_tile_trace ? tiles : 0;
+    return SDFR_OK;
+}
 
 extern "C" int sdfr_decoder_destroy(sdfr_decoder* d) {
     if (!d) return SDFR_OK;
@@ -208,6 +217,7 @@ extern "C" int sdfr_mlp_forward(const sdfr_decoder* d, const float* inputs, int6
     if (n == 0) return SDFR_OK;
     MlpParams P = d->proto;
     P.inputs = inputs; P.n = n; P.sdf = sdf; P.maskbuf = mask_ws; P.trace = g_trace;
+    P.tile_trace = g_tile_trace; P.tile_trace_cap = g_tile_trace_cap;
     const int grid = sdfr_cdiv(n, 64);
     if (d->has_ln) sdfr_launch_ln(P, d->HP, false, grid, 1, (hipStream_t)stream);        // LayerNorm decoders: no mask saving
     else if (d->HP == 512) sdfr_launch_fwd_f32_512(P, n, mask_ws != nullptr, (hipStream_t)stream);
@@ -252,8 +262,60 @@ extern "C" int sdfr_mlp_forward_ordered(const sdfr_decoder* d, const float* inpu
     if (n == 0) return SDFR_OK;
     MlpParams P = d->proto;
     P.inputs = inputs; P.n = n; P.sdf = sdf; P.maskbuf = mask_ws; P.trace = g_trace;
+    P.tile_trace = g_tile_trace; P.tile_trace_cap = g_tile_trace_cap;
     sdfr_launch_fwd_f32_512_ordered(P, n, order, order_rows, (hipStream_t)stream);
     SDFR_LAUNCH_CHECK();
+    return SDFR_OK;
+}
+
+// sdfr_mlp_forward_ordered whose order follows the last pass (tile_balance.h): the launch reads the state's order and adds each tile's cost
+// to the state, and a small kernel behind it ranks the chunks heaviest first for the next call.  The same outputs bit for bit
+// whatever the state holds.  No host read, no synchronisation, the state's pointers alone: a captured graph replays it.
+extern "C" int64_t sdfr_mlp_balance_bytes(int64_t order_rows) {
+    return order_rows > 0 && order_rows < (int64_t)1 << 31 ? sdfr_tb_state_words(order_rows) * 4 : 0;
+}
+
+extern "C" int sdfr_mlp_balance_init(void* state, const int32_t* order, int64_t order_rows, void* stream) {
+    SDFR_REQUIRE(state && order, "sdfr_mlp_balance_init: NULL argument");
+    SDFR_REQUIRE(order_rows > 0 && order_rows < (int64_t)1 << 31, "sdfr_mlp_balance_init: order_rows=%lld out of range", (long long)order_rows);
+    // no decoder here to name the device: the state itself does.  A launch from another current device would write it across devices
+    int cur = -1;
+    hipPointerAttribute_t attr;
+    SDFR_HIP_CHECK(hipGetDevice(&cur));
+    SDFR_HIP_CHECK(hipPointerGetAttributes(&attr, state));
+    SDFR_REQUIRE(attr.type == hipMemoryTypeDevice && attr.device == cur,
+                 "sdfr_mlp_balance_init: the state must be device memory of the current device %d (the launch stream's); it is %s of device %d", cur,
+                 attr.type == hipMemoryTypeDevice ? "memory" : "not device memory", attr.device);
+    sdfr_launch_tile_balance_init((int32_t*)state, order, order_rows, (hipStream_t)stream);
+    SDFR_LAUNCH_CHECK();
+    return SDFR_OK;
+}
+
+extern "C" int sdfr_mlp_forward_balanced(const sdfr_decoder* d, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, void* state,
+                                         int64_t order_rows, void* stream) {
+    SDFR_REQUIRE(d && inputs && sdf && state, "sdfr_mlp_forward_balanced: NULL argument");
+    SDFR_REQUIRE(n >= 0 && n < (int64_t)1 << 31, "sdfr_mlp_forward_balanced: n=%lld out of range", (long long)n);
+    SDFR_REQUIRE(order_rows > 0, "sdfr_mlp_forward_balanced: order_rows=%lld must be positive", (long long)order_rows);
+    SDFR_REQUIRE(n % order_rows == 0, "sdfr_mlp_forward_balanced: n=%lld is not a multiple of order_rows=%lld", (long long)n, (long long)order_rows);
+    SDFR_REQUIRE(d->HP == 512 && !d->has_ln, "sdfr_mlp_forward_balanced: needs a float32 decoder of padded width 512 without LayerNorm (this one: %d%s)",
+                 d->HP, d->has_ln ? ", LayerNorm" : "");
+    SDFR_REQUIRE(!mask_ws || ((n + 127) / 128) * 128 * (int64_t)(d->n_lin - 1) < (int64_t)1 << 31,
+                 "sdfr_mlp_forward_balanced: n=%lld rows with masks of %d layers exceed the kernel's line index", (long long)n, d->n_lin - 1);
+    SDFR_DEVICE_CHECK(d, "sdfr_mlp_forward_balanced");
+    if (n == 0) return SDFR_OK;
+    int32_t* st = (int32_t*)state;
+    const bool ranked = sdfr_tb_ranked(order_rows);          // (larger orders: tens of rounds, nothing to gain -- the static order, no ranking)
+    MlpParams P = d->proto;
+    P.inputs = inputs; P.n = n; P.sdf = sdf; P.maskbuf = mask_ws; P.trace = g_trace;
+    P.tile_trace = g_tile_trace; P.tile_trace_cap = g_tile_trace_cap;
+    P.tile_cost = ranked ? st + sdfr_tb_cost_word(order_rows) : nullptr;
+    P.tile_at = st + sdfr_tb_at_word(order_rows);
+    sdfr_launch_fwd_f32_512_ordered(P, n, st + sdfr_tb_order_word(order_rows), order_rows, (hipStream_t)stream);
+    SDFR_LAUNCH_CHECK();
+    if (ranked) {
+        sdfr_launch_tile_balance(st, order_rows, (hipStream_t)stream);
+        SDFR_LAUNCH_CHECK();
+    }
     return SDFR_OK;
 }
 

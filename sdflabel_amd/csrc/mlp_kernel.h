@@ -24,6 +24,7 @@
 #include "sdfr_common.h"
 #include "kc_slots.h"
 #include "kcj_slots.h"
+#include "tile_balance.h"
 #include <math.h>
 #include <type_traits>
 
@@ -117,7 +118,15 @@ struct MlpParams {
     int32_t* t_unresolved;       // += rays still active when the step budget ran out
     const float* Wkj;            // exact-f32 backward, k-major image: [layer][k][sdfr_kcj_col(in-feature)] floats at float offset 4 * off_b (KCJ below)
     int jcompact;                // 1: the 16-row mask-fed Jacobian skips features whose mask bit is 0 in every row of a tile (0: the full K chain)
+    int32_t* tile_cost;          // ORDER kernels: NULL, or [sdfr_tb_chunks(gather_rows)] costs (tile_balance.h): each tile adds the K extent its
+    const int32_t* tile_at;      // compacted products walked to the word of the chunk it evaluates, tile_at[its place in the order]
+                                 // (sdfr_mlp_forward_balanced)
+    unsigned long long* tile_trace;   // builds with -DSDFR_MLP_TRACE: per-workgroup records of the forward kernels (sdfr_debug_set_tile_trace,
+    int64_t tile_trace_cap;           // SDFR_TILE_TRACE_WORDS words each, workgroups >= tile_trace_cap write nothing), else unused
 };
+// One record of the tile trace (tools/tile_gantt.py): shader clock at the workgroup's start and end, the 100 MHz constant clock at both (the
+// shader clocks of two XCDs need not agree; the constant clock orders tiles across the device), where it ran, and blockIdx.x.
+#define SDFR_TILE_TRACE_WORDS 6
 
 struct sdfr_decoder {
     int device;
@@ -345,6 +354,18 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
 #define SDFR_STAMP(l, i) do { } while (0)
 #endif
     SDFR_STAMP(8, 0);
+#ifdef SDFR_MLP_TRACE
+    // tile trace: every workgroup of a forward launch, thread 0: [start cycles, start 100 MHz, end cycles, end 100 MHz, place, blockIdx.x];
+    // place = XCC_ID << 32 | HW_ID (CU 11:8, SH 12, SE 15:13).  The end is stamped behind the tile's sdf store.
+    const bool tt_on = !JAC && !TAIL && P.tile_trace && tid == 0 && blockIdx.y == 0 && (int64_t)blockIdx.x < P.tile_trace_cap;
+    if (tt_on) {
+        unsigned long long* tt = P.tile_trace + (int64_t)blockIdx.x * SDFR_TILE_TRACE_WORDS;
+        tt[0] = __builtin_amdgcn_s_memtime();
+        tt[1] = __builtin_amdgcn_s_memrealtime();
+        tt[4] = ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11));
+        tt[5] = blockIdx.x;
+    }
+#endif
     // ---- which rows does this tile hold ------------------------------------------------------------------
     // MODE 4: a pool of persistent workgroups; each trip of this loop fetches one tile (t_rt rays) from the launch's device counter and marches
     // it through the stage.  Every other mode: one trip, tile = blockIdx.x.
@@ -477,6 +498,9 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
                 slots[tid] = ok ? (int)row : -1;
                 reinterpret_cast<int*>(gy)[tid] = ok ? (int)((row >> 7) * P.n_mfma * 128 + (row & 127)) : -1;
             }
+            // the tile's cost (tile_balance.h) gathers in LDS, in the last of the 128 ints kept for rows[] (PT = 64 of them are rows)
+            static_assert(!ORDER || PT <= 64, "ORDER: rows[127] is the tile's cost");
+            if (tid == 0) rows[127] = 0;
         } else
         if (tid < PT) rows[tid] = TAIL ? (int)((int64_t)blockIdx.x * PT + tid) : (int)(r0 + (tid < n_valid ? tid : 0));
     }
@@ -1227,6 +1251,13 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
                 if (lane < padded - tot) reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(tot + lane)] = sdfr_kcd_pad_entry();
             }
             kc_n = padded;
+            // ORDER: what this layer's operand adds to the tile's cost (tile_balance.h).  Thread 0 alone zeroes, adds to and reads the word;
+            // the add is written as an LDS atomic all the same, for the instruction it gives: one ds_add_u32 without a result.  A plain
+            // rows[127] += ... is a read, an add and a write through a VGPR in the middle of the epilogue, and the register allocator
+            // answers with two more spilled VGPRs and 8 B more scratch per lane (9 / 32 B against 7 / 24 B, as the parent has).
+            if constexpr (ORDER) {
+                if (tid == 0) __hip_atomic_fetch_add(rows + 127, sdfr_tb_layer_cost(tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
         };
         auto epilogue = [&](auto inj_tag) {
             constexpr bool INJ = decltype(inj_tag)::value;
@@ -1462,6 +1493,11 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
             } else if constexpr (ORDER) {
                 const int row = slots[tid];
                 if (row >= 0 && (!P.skip || !P.skip[row / P.skip_rows])) P.sdf[row] = o;
+                // the tile's cost, once, behind the last layer: an integer add, so that the crops of a launch sum in any order
+                if (P.tile_cost && tid == 0) {
+                    const int place = sdfr_tb_place_of_tile(tile, P.gather_rows);
+                    atomicAdd(P.tile_cost + sdfr_tb_cost_index(P.tile_at[place], place, P.gather_rows), rows[127]);
+                }
             } else {
                 if (tid < n_valid) {
                     const int64_t row = (int64_t)tile * PT + tid;
@@ -1470,6 +1506,13 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
             }
         }
     }
+#ifdef SDFR_MLP_TRACE
+    if (tt_on) {
+        unsigned long long* tt = P.tile_trace + (int64_t)blockIdx.x * SDFR_TILE_TRACE_WORDS;
+        tt[2] = __builtin_amdgcn_s_memtime();
+        tt[3] = __builtin_amdgcn_s_memrealtime();
+    }
+#endif
     if constexpr (TAIL) {
         // another pass while a ray of the tile is still marching and the step budget lasts
         --t_left;
@@ -1974,6 +2017,8 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
 // allocation and scheduling by several percent -- CDNA guide, methodology rule 19 -- so the hot kernels are compiled alone)
 void sdfr_launch_fwd_f32_512(const MlpParams& P, int64_t n, bool save_masks, hipStream_t s);    // mlp_fwd32.hip
 void sdfr_launch_fwd_f32_512_ordered(const MlpParams& P, int64_t n, const int32_t* order, int64_t order_rows, hipStream_t s);
+void sdfr_launch_tile_balance_init(int32_t* state, const int32_t* order, int64_t order_rows, hipStream_t s);      // mlp_balance.hip
+void sdfr_launch_tile_balance(int32_t* state, int64_t order_rows, hipStream_t s);                                  // mlp_balance.hip
 int sdfr_fwd_f32_512_np();                                                                        // its point tiles per workgroup
 void sdfr_launch_fwd_f16_512(const MlpParams& P, int64_t n, bool save_masks, hipStream_t s);   // mlp_fwd16.hip
 void sdfr_launch_fwd_f16_512_half_tiles(const MlpParams& P, int64_t n, hipStream_t s);          // mlp_fwd16.hip (64-row tiles, masks)

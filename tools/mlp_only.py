@@ -1,7 +1,8 @@
 """Run only the decoder forward (G=64000) a few times -- target for rocprofv3 PMC passes.
-usage: mlp_only.py [launches] [f32|f16|split] [dropin|plain|ordered]
+usage: mlp_only.py [launches] [f32|f16|split] [dropin|plain|ordered|balanced]
 dropin (default): the drop-in Decoder(inputs) call.  plain / ordered (f32): sdfr_mlp_forward / sdfr_mlp_forward_ordered with a mask buffer, as
-BatchRenderer launches them -- ordered with the 4x4x4-block tile order of sdfr_grid_tile_order."""
+BatchRenderer launches them -- ordered with the 4x4x4-block tile order of sdfr_grid_tile_order; balanced: sdfr_mlp_forward_balanced on that
+order (the renderer's default: the launch order of the tiles follows the last launch's costs, and the ranking kernel runs behind each)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.nn.functional as F
@@ -25,12 +26,17 @@ else:
     h = dec.handle(torch.device(dev)).h
     sdf = torch.empty(G, device=dev)
     mw = torch.zeros(int(L.sdfr_decoder_mask_words(h, G)), dtype=torch.int32, device=dev)
-    if how == "ordered":
+    if how in ("ordered", "balanced"):
         order = torch.empty(G, dtype=torch.int32)
         _lib.check(L.sdfr_grid_tile_order(40, P(order)), "sdfr_grid_tile_order")
         order = order.to(dev)
+    if how == "balanced":
+        state = torch.empty(int(L.sdfr_mlp_balance_bytes(G)) // 4, dtype=torch.int32, device=dev)
+        _lib.check(L.sdfr_mlp_balance_init(P(state), P(order), G, _lib.stream_ptr()), "sdfr_mlp_balance_init")
     for _ in range(n):
-        if how == "ordered":
+        if how == "balanced":
+            _lib.check(L.sdfr_mlp_forward_balanced(h, P(inputs), G, P(sdf), P(mw), P(state), G, _lib.stream_ptr()), "sdfr_mlp_forward_balanced")
+        elif how == "ordered":
             _lib.check(L.sdfr_mlp_forward_ordered(h, P(inputs), G, P(sdf), P(mw), P(order), G, _lib.stream_ptr()), "sdfr_mlp_forward_ordered")
         else:
             _lib.check(L.sdfr_mlp_forward(h, P(inputs), G, P(sdf), P(mw), _lib.stream_ptr()), "sdfr_mlp_forward")
