@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 416        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 417        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -47,7 +47,7 @@ extern "C" {
  * refined labels, sdfr_mesh_raster and sdfr_verify_*; 413: the export of training crops, sdfr_crop_*; 414: synthetic
  * bootstrap crops, sdfr_synth_*; 415: signed distances to meshes and surface samples, sdfr_mesh_sdf* and sdfr_mesh_surface_*; 416: the
  * grid forward's launch order from the last pass, sdfr_mlp_balance_* and sdfr_mlp_forward_balanced, and the per-workgroup tile trace of trace
- * builds, sdfr_debug_set_tile_trace).  A caller built
+ * builds, sdfr_debug_set_tile_trace; 417: training the decoder, sdfr_decoder_train_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -1112,6 +1112,50 @@ int64_t sdfr_mesh_surface_ws_bytes(int B, int64_t T);
 int sdfr_mesh_surface_points(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const int64_t* voff, const int64_t* toff,
                              const float* uniforms, int64_t S, const int64_t* soff, int B, void* ws, int64_t ws_bytes, float* points,
                              int32_t* triangle, int32_t* flags, void* stream);
+
+/*
+ * Training the DeepSDF decoder (csrc/mlp_train.hip): the forward of Decoder.forward in train() mode
+ * (sdfrenderer/deepsdf/networks/deep_sdf_decoder_scale.py:78-107, dropout included) with its activations kept, and the gradient of a scalar
+ * loss with respect to the input rows AND the weights.  Exact float32 (v_mfma_f32_32x32x2_f32, k in order, bias last); no half path, no
+ * LayerNorm decoders.
+ *
+ * The weights change every step, so W[l] / b[l] are DEVICE pointers to plain float32 [out_dim[l]][in_dim[l]] / [out_dim[l]] (the arrays W, b,
+ * dW, db themselves are host arrays of n_lin device pointers).  The decoder is described as for sdfr_decoder_create: n_lin, in_dim, out_dim,
+ * inj_n, inj_off, n_inputs, use_tanh; out_dim up to 512, in_dim up to 1024, n up to 2^26.
+ *
+ *   forward    a_l = drop(relu(xin_l W_l^T + b_l)); xin_0 = inputs, xin_{l+1} = cat(a_l, inputs[:, inj_off[l+1] : + inj_n[l+1]]).
+ *              sdf[n] = tanh(y1), y1 = use_tanh ? tanh(y) : y, y the last linear.
+ *   dropout    stateless: unit (l, row, j) of a layer whose bit l is set in drop_layers is kept when the top 24 bits of
+ *              mix64(seed ^ mix64((row << 14 | l << 10 | j) * 0x9E3779B97F4A7C15 + 1)) are >= rint(drop_p 2^24) (mix64: the splitmix64 finaliser,
+ *              csrc/train_cells.h); a kept unit is multiplied by the float32 value 1 / (1 - drop_p).  drop_p = 0 takes no hash.  This is the
+ *              library's own random stream, not torch's.
+ *   backward   d of the last linear = g_sdf (1 - out^2) (1 - y1^2 with use_tanh); d_{l-1} = (d_l W_l) * (a_{l-1} > 0 ? 1 / (1 - drop_p) : 0) -- the
+ *              stored activation is the mask; g_inputs[n][n_inputs] = layer 0's term plus the re-injected columns' terms of the injection
+ *              layers in ascending l; dW_l = d_l^T xin_l and db_l = the column sums of d_l: the rows are cut into chunks of 1024 in order, a
+ *              chunk is summed in row order, and the chunk sums are added in chunk order.  No atomics: dW / db are functions of n and the shapes
+ *              and have the same bits on every run; sdf[i] and g_inputs[i] do not depend on the batch or (with drop_p = 0) on i.
+ *   workspace  sdfr_decoder_train_bytes(...) bytes (-1: a description the kernels refuse), float32 words, with chunks = ceil(n / 1024) and
+ *              nh = n_lin - 1:
+ *                header   16 words: [0] float 1 / (1 - drop_p) of the forward that filled the workspace, [1] int32 the drop_layers it applied
+ *                x0       [n][in_dim[0]]                the input rows
+ *                act[l]   [n][in_dim[l + 1]], l < nh    a_l (after ReLU, dropout and its scale) in columns 0 .. out_dim[l] - 1, the re-injected
+ *                                                       input columns of layer l + 1 behind them; act[l] starts at word
+ *                                                       16 + n (in_dim[0] + in_dim[1] + ... + in_dim[l])
+ *                tail     [n][2]                        y1 and out
+ *                delta    2 x [n][max out_dim]          d_l in half l & 1
+ *                ginj[l]  [n][inj_n[l]], l >= 1
+ *                part     [chunks][out][in] then [chunks][out]: the partials of the layer the backward handled last (layer 0); the section is
+ *                         sized chunks * max_l (out_dim[l] in_dim[l] + out_dim[l])
+ *              sdfr_decoder_train_backward reads what the forward of the same n left there.  A workspace that is too small is an error.
+ * Launches: 1 + n_lin (forward), 1 + 3 n_lin (backward); no host synchronisation, no host read, no memset.
+ */
+int64_t sdfr_decoder_train_bytes(int n_lin, const int* in_dim, const int* out_dim, const int* inj_n, const int* inj_off, int n_inputs, int64_t n);
+int sdfr_decoder_train_forward(int n_lin, const int* in_dim, const int* out_dim, const int* inj_n, const int* inj_off, int n_inputs,
+                               int use_tanh, const float* const* W, const float* const* b, const float* inputs, int64_t n, float drop_p,
+                               int drop_layers, int64_t seed, float* sdf, void* ws, int64_t ws_bytes, void* stream);
+int sdfr_decoder_train_backward(int n_lin, const int* in_dim, const int* out_dim, const int* inj_n, const int* inj_off, int n_inputs,
+                                int use_tanh, const float* const* W, const float* g_sdf, int64_t n, void* ws, int64_t ws_bytes,
+                                float* const* dW, float* const* db, float* g_inputs, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (8 waves * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */
