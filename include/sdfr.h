@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 417        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 418        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -47,7 +47,8 @@ extern "C" {
  * refined labels, sdfr_mesh_raster and sdfr_verify_*; 413: the export of training crops, sdfr_crop_*; 414: synthetic
  * bootstrap crops, sdfr_synth_*; 415: signed distances to meshes and surface samples, sdfr_mesh_sdf* and sdfr_mesh_surface_*; 416: the
  * grid forward's launch order from the last pass, sdfr_mlp_balance_* and sdfr_mlp_forward_balanced, and the per-workgroup tile trace of trace
- * builds, sdfr_debug_set_tile_trace; 417: training the decoder, sdfr_decoder_train_*).  A caller built
+ * builds, sdfr_debug_set_tile_trace; 417: training the decoder, sdfr_decoder_train_*; 418: encoding shapes under a
+ * frozen decoder, sdfr_encode_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -1156,6 +1157,50 @@ int sdfr_decoder_train_forward(int n_lin, const int* in_dim, const int* out_dim,
 int sdfr_decoder_train_backward(int n_lin, const int* in_dim, const int* out_dim, const int* inj_n, const int* inj_off, int n_inputs,
                                 int use_tanh, const float* const* W, const float* g_sdf, int64_t n, void* ws, int64_t ws_bytes,
                                 float* const* dW, float* const* db, float* g_inputs, void* stream);
+
+/* ---- encoding shapes under a frozen decoder (csrc/encode.hip, SDFR_VERSION 418) ----
+ *
+ * DeepSDF's "reconstruct": the latent of a shape the decoder was not trained on, fitted to the shape's SDF samples with the decoder frozen.  One
+ * iteration is  sdfr_encode_rows -> a decoder forward that saves its masks -> sdfr_mlp_jacobian with an identity index list ->
+ * sdfr_encode_reduce -> sdfr_encode_step, for B shapes at once.  All pointers are device pointers; no atomics, no memset, no host
+ * synchronisation, the same bits on every run, and a shape's results do not depend on B or on its position in the batch.  Float64 and float32
+ * operations are rounded one by one (no contraction).  csrc/encode_cells.h holds the per-element rules; DESIGN.md 7k.
+ *
+ *   flags[b]   bit 0 (1) the shape has no samples; bit 1 (2) no row with a finite prediction and target; bit 2 (4) the latent was not stepped;
+ *              bit 3 (8) soff is broken at this shape (soff[b] < 0, soff[b + 1] < soff[b] or soff[b + 1] > S), or draw = 0 with k > count_b.
+ *              sdfr_encode_rows stores bits 0 and 3 and clears the others; the reduce and the step add theirs.  The table lives on the device,
+ *              so a broken entry cannot be a return code: the shape's rows are zero, nothing is read through it, and it is never stepped.
+ *
+ * sdfr_encode_rows: samples [S][4] = x y z sdf, soff int64 [B + 1] (shape b owns samples soff[b] .. soff[b + 1] - 1, count_b of them), z [B][L]
+ *   the raw latents.  Row s < k of shape b takes sample soff[b] + s with draw = 0 and soff[b] + mulhi64(mix64(seed ^ mix64((iter << 40 | (shape0 + b)
+ *   << 24 | s) * 0x9E3779B97F4A7C15 + 1)), count_b) with draw = 1 (with replacement; mix64: the splitmix64 finaliser of csrc/train_cells.h; mulhi64:
+ *   the upper 64 bits of the 128-bit product; the library's own random stream).  Writes inputs [B k][L + 3] = (zn[b], x y z), target [B k] and
+ *   zn [B][L]: z / max(||z||, 1e-12) in float32 with unit != 0 (the rule of sdfr_params_forward), z otherwise.  A shape with flag bit 0 or 3
+ *   gets zero rows and zero targets.  inputs == NULL: zn and flags only.  shape0: the index the first
+ *   shape has in the caller's whole batch, for the hash alone (a caller that stages its shapes in groups draws the same rows whatever the groups).
+ *   1 <= L <= 256, 1 <= k <= 2^20, shape0 + B <= 65535, 0 <= iter < 2^24.
+ *
+ * sdfr_encode_reduce: pred [B k] (the decoder's values), target [B k], J [B k][Jstride] whose latent columns are columns 0 .. L - 1.  With
+ *   cp = clamp(p, -clamp, clamp), ct likewise, over the rows whose p and t are both finite (n_ok of them), in float64:
+ *   loss[b] = mean |cp - ct|;  g_zn[b][c] = mean sgn(cp - ct) [-clamp <= p <= clamp] J[i][c]  (sgn(0) = 0; a row whose factor is 0 adds nothing,
+ *   whatever its J holds); both are 0 and bit 1 of flags[b] is set when n_ok = 0.  The rows of a shape are cut into chunks of 1024 in order; in a
+ *   chunk, accumulator j < 64 sums rows j, j + 64, ... in ascending order and the accumulators are folded by halves (j takes j + 32, then
+ *   j + 16, ... j + 1); the chunk sums are added in chunk order.  ws: sdfr_encode_ws_bytes(B, k, L) bytes (-1: sizes the kernels refuse),
+ *   aligned to 8.  Two launches.
+ *
+ * sdfr_encode_step: Adam (betas 0.9 / 0.999, eps 1e-8, the update of sdfr_solver_step) on z [B][L] with state m, v [B][L], step count t >= 1
+ *   and learning rate lr per call; 1 - beta^t is formed in double on the host.  The gradient is float32(g_zn) taken through the normalisation
+ *   with unit != 0 (the formula of sdfr_params_backward) and float32(g_zn) + code_reg z / ||z|| (nothing added at z = 0) otherwise.  A shape
+ *   whose flags hold bit 0, 1 or 3, or whose gradient has a non-finite element, keeps z, m and v and gets bit 2.  history != NULL:
+ *   history[(t - 1) history_stride + b] = float32(loss[b]).
+ */
+int64_t sdfr_encode_ws_bytes(int B, int64_t k, int L);
+int sdfr_encode_rows(const float* samples, int64_t S, const int64_t* soff, int B, int shape0, int64_t k, int draw, int64_t seed, int64_t iter, const float* z,
+                     int L, int unit, float* inputs, float* target, float* zn, int32_t* flags, void* stream);
+int sdfr_encode_reduce(const float* pred, const float* target, const float* J, int Jstride, int L, int B, int64_t k, float clamp, void* ws,
+                       int64_t ws_bytes, double* loss, double* g_zn, int32_t* flags, void* stream);
+int sdfr_encode_step(float* z, float* m, float* v, int L, int B, int unit, const double* g_zn, const double* loss, int32_t* flags, float code_reg,
+                     float lr, int t, float* history, int64_t history_stride, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (8 waves * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

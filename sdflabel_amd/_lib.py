@@ -9,7 +9,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDFR_LIB") or os.path.join(_HERE, "lib", "libsdfr_hip.so")     # SDFR_LIB: A/B builds (tools/ab_build.sh)
 
-ABI_VERSION = 417          # include/sdfr.h SDFR_VERSION
+ABI_VERSION = 418          # include/sdfr.h SDFR_VERSION
 _lib = None
 
 # name -> (restype, argtypes); mirrors include/sdfr.h one to one
@@ -249,6 +249,14 @@ _PROTOS = {
                                            POINTER(c_void_p), c_void_p, c_int64, c_float, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "sdfr_decoder_train_backward": (c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_int, POINTER(c_void_p),
                                             c_void_p, c_int64, c_void_p, c_int64, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p]),
+    # encoding shapes under a frozen decoder: the iteration's rows, per-shape loss and latent gradient, Adam on the latents (csrc/encode.hip)
+    "sdfr_encode_ws_bytes": (c_int64, [c_int, c_int64, c_int]),
+    "sdfr_encode_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "sdfr_encode_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_float, c_void_p, c_int64, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "sdfr_encode_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p,
+                                 c_int64, c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -6,6 +6,7 @@
 // (:99-100); and the matching backward.  Compiled with -ffp-contract=off.
 #include "sdfr_common.h"
 #include "solver.h"
+#include "latent_cells.h"
 
 __global__ __launch_bounds__(256) void sdfr_params_forward_kernel(const float* __restrict__ yaw, const float* __restrict__ trans,
                                                                  const float* __restrict__ latent, int L,
@@ -14,10 +15,7 @@ __global__ __launch_bounds__(256) void sdfr_params_forward_kernel(const float* _
                                                                  float* __restrict__ latnorm) {
     const int b = blockIdx.y;
     const int NI = L + 3;
-    // ||latent||_2, max(., 1e-12) as F.normalize does
-    float ss = 0.f;
-    for (int c = 0; c < L; ++c) ss += latent[b * L + c] * latent[b * L + c];
-    const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+    const float nrm = latent_norm(latent + b * L, L);            // ||latent||_2, max(., 1e-12) as F.normalize does (latent_cells.h)
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         latnorm[b] = nrm;
         const float c = cosf(yaw[b]), s = sinf(yaw[b]);
@@ -57,9 +55,7 @@ __global__ __launch_bounds__(256) void sdfr_params_plan_kernel(const float* __re
                                                               int32_t* __restrict__ reuse, int32_t* __restrict__ n_full) {
     const int b = blockIdx.y;
     const int NI = L + 3;
-    float ss = 0.f;
-    for (int c = 0; c < L; ++c) ss += latent[b * L + c] * latent[b * L + c];
-    const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+    const float nrm = latent_norm(latent + b * L, L);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         latnorm[b] = nrm;
         const float c = cosf(yaw[b]), s = sinf(yaw[b]);
@@ -167,9 +163,8 @@ __global__ __launch_bounds__(64) void sdfr_params_backward_kernel(const float* _
     g_yaw[b] = (-s) * g[0] + c * g[2] + (-c) * g[8] + (-s) * g[10];
     g_trans[b * 3] = g[3]; g_trans[b * 3 + 1] = g[7]; g_trans[b * 3 + 2] = g[11];
     const float nrm = latnorm[b];
-    float dot = 0.f;
-    for (int i = 0; i < L; ++i) dot += (latent[b * L + i] / nrm) * g_latn[b * L + i];
-    for (int i = 0; i < L; ++i) g_latent[b * L + i] = (g_latn[b * L + i] - (latent[b * L + i] / nrm) * dot) / nrm;
+    const float dot = latent_unit_dot(latent + b * L, g_latn + b * L, L, nrm);
+    for (int i = 0; i < L; ++i) g_latent[b * L + i] = latent_unit_grad(latent[b * L + i], g_latn[b * L + i], nrm, dot);
 }
 
 extern "C" int sdfr_params_backward(const float* yaw, const float* latent, int L, const float* latnorm, const float* g_pose,
@@ -368,9 +363,8 @@ __global__ __launch_bounds__(PLB_THREADS) void sdfr_pose_latent_backward_kernel(
         g_trans[b * 3] = red[3][0]; g_trans[b * 3 + 1] = red[7][0]; g_trans[b * 3 + 2] = red[11][0];
         if (LAT) {
             const float nrm = latnorm[b];
-            float dot = 0.f;
-            for (int i = 0; i < L; ++i) dot += (latent[b * L + i] / nrm) * s_latn[i];
-            for (int i = 0; i < L; ++i) g_latent[b * L + i] = (s_latn[i] - (latent[b * L + i] / nrm) * dot) / nrm;
+            const float dot = latent_unit_dot(latent + b * L, s_latn, L, nrm);
+            for (int i = 0; i < L; ++i) g_latent[b * L + i] = latent_unit_grad(latent[b * L + i], s_latn[i], nrm, dot);
         } else {                                                        // pose-only: the latent is not a variable
             for (int i = 0; i < L; ++i) { g_latn[b * L + i] = 0.f; g_latent[b * L + i] = 0.f; }
         }

@@ -4,6 +4,7 @@
 // params / grads: one flat structure-of-arrays buffer  [ yaw(B) | trans(B,3) | scale(B) | latent(B,L) ].
 #pragma once
 #include "sdfr_common.h"
+#include "latent_cells.h"
 
 __device__ __forceinline__ void sdfr_solver_crop(const int b, const int B, float* params, const float* grads, int L,   /* (no __restrict__: the fused tail has just written grads through other pointers) */
                                                  const float* __restrict__ loss2d, const float* __restrict__ loss3d,
@@ -26,20 +27,12 @@ __device__ __forceinline__ void sdfr_solver_crop(const int b, const int B, float
     const float* g = grads;
     const int t = adam_t[b] + 1;
     adam_t[b] = t;
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-    // 1 - beta2 and 1 - beta2^t as torch forms them (in double, then rounded).  In float32, 1.f - 0.999f is 0.99998713e-3: it put the second
-    // moment 1.3e-5 below the reference's float32 run, and 1 - powf(0.999f, t) is off by as much at small t; -expm1(t ln beta2) is not
-    const float omb2 = 0.001f;
+    const float b1 = 0.9f;
+    // 1 - beta2^t as torch forms it (in double, then rounded): 1 - powf(0.999f, t) is off by 1.3e-5 at small t; -expm1(t ln beta2) is not.
+    // The update itself is latent_adam (latent_cells.h), shared with the shape encoder.
     const float bc1 = 1.f - powf(b1, (float)t), bc2 = -expm1f((float)t * -1.0005003335835335e-3f);
-    for (int i = 0; i < 4; ++i) {                                        // Adam on yaw, trans (:34-36,47-49)
-        float m = adam_m[b * 4 + i], v = adam_v[b * 4 + i];
-        const float gi = g[at(i)];
-        m = b1 * m + (1.f - b1) * gi;
-        v = b2 * v + omb2 * gi * gi;
-        adam_m[b * 4 + i] = m; adam_v[b * 4 + i] = v;
-        const float denom = sqrtf(v) / sqrtf(bc2) + eps;
-        p[at(i)] -= (lr_adam / bc1) * (m / denom);
-    }
+    for (int i = 0; i < 4; ++i)                                          // Adam on yaw, trans (:34-36,47-49)
+        latent_adam(&p[at(i)], &adam_m[b * 4 + i], &adam_v[b * 4 + i], g[at(i)], lr_adam, bc1, bc2);
     p[at(4)] -= lr_scale * g[at(4)];                                      // SGD on scale, latent (:37-38,50-51)
     for (int i = 0; i < L; ++i) p[at(5 + i)] -= lr_latent * g[at(5 + i)];
 }

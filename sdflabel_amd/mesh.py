@@ -104,6 +104,11 @@ class Mesh:
         from .sdf_samples import mesh_sdf_many
         return mesh_sdf_many([self], [points], want_sign=want_sign).sdf
 
+    def encode(self, dsdf, n=500000, generator=None, **kw):
+        """the latent of this (lattice-frame) mesh under the frozen decoder dsdf: encode.encode_meshes on this one mesh -> Encoded"""
+        from .encode import encode_meshes
+        return encode_meshes(dsdf, [self], n=n, generator=generator, **kw)
+
     def save(self, path, drop_degenerate=False):
         """binary little-endian PLY (with normals when the mesh has them) or OBJ, by extension.  Host code."""
         v, n, f = self.vertices_numpy(), self.normals_numpy(), self.faces_numpy(drop_degenerate)
@@ -329,6 +334,17 @@ def lattice_sdf(dsdf, latents, R, staging_bytes=STAGING_BYTES):
     return sdf
 
 
+def decoder_rows(handle, fwd, f16, inputs, n, sdf, J, sel, masks, idx, cnt, st):
+    """One staged chunk of n decoder rows: the forward `fwd` of _decoder_mode (masks saved) and sdfr_mlp_jacobian with the identity index list
+    idx [n] / cnt [1] = n, into sdf [n], J [n][n_inputs] and sel [n].  The two launches decoder_at makes per chunk and encode.encode_many makes
+    per iteration.  masks is None for LayerNorm decoders: they save none, and their Jacobian recomputes the forward."""
+    L = _lib.lib()
+    P, ck = _lib.ptr, _lib.check
+    ck(fwd(handle.h, P(inputs), n, P(sdf), P(masks), st), fwd.__name__)
+    ck(L.sdfr_mlp_jacobian(handle.h, P(inputs), n, 1, P(idx), n, P(cnt), P(J), P(sel), P(sdf) if masks is not None else None, P(masks),
+                           2 if f16 else 0, st), "sdfr_mlp_jacobian")
+
+
 def decoder_at(dsdf, latents, shape_of, points, staging_bytes=STAGING_BYTES):
     """The decoder, its Jacobian and the Newton projection at `points` [n][3] of the shapes shape_of [n] (int64 rows of latents): the calls
     Grid3D.get_surface_points makes for its band, with an identity index list.  Returns (projected points p - sdf n, unit normals n, sdf)."""
@@ -353,10 +369,7 @@ def decoder_at(dsdf, latents, shape_of, points, staging_bytes=STAGING_BYTES):
             sel = torch.empty((n,), dtype=torch.float32, device=dev)
             sdf = val[r0:r0 + n]
             masks = None if handle.has_ln else torch.empty((int(L.sdfr_decoder_mask_words(handle.h, n)),), dtype=torch.int32, device=dev)
-            ck(fwd(handle.h, P(inputs), n, P(sdf), P(masks), st), fwd.__name__)
-            # LayerNorm decoders save no masks: their Jacobian recomputes the forward, as mlp_jacobian does for them
-            ck(L.sdfr_mlp_jacobian(handle.h, P(inputs), n, 1, P(idx), n, P(cnt), P(J), P(sel), P(sdf) if masks is not None else None, P(masks),
-                                   2 if f16 else 0, st), "sdfr_mlp_jacobian")
+            decoder_rows(handle, fwd, f16, inputs, n, sdf, J, sel, masks, idx, cnt, st)
             ck(L.sdfr_surface_project(P(inputs[:, Ld:]), NI, P(sdf), n, 1, P(idx), n, P(cnt), P(J), NI, Ld, P(proj[r0:]), None, P(nrm[r0:]), st),
                "sdfr_surface_project")
     return proj, nrm, val
