@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 418        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 419        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -48,7 +48,8 @@ extern "C" {
  * bootstrap crops, sdfr_synth_*; 415: signed distances to meshes and surface samples, sdfr_mesh_sdf* and sdfr_mesh_surface_*; 416: the
  * grid forward's launch order from the last pass, sdfr_mlp_balance_* and sdfr_mlp_forward_balanced, and the per-workgroup tile trace of trace
  * builds, sdfr_debug_set_tile_trace; 417: training the decoder, sdfr_decoder_train_*; 418: encoding shapes under a
- * frozen decoder, sdfr_encode_*).  A caller built
+ * frozen decoder, sdfr_encode_*; 419: shape completion from one view, sdfr_view_samples and
+ * sdfr_bound_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -1201,6 +1202,47 @@ int sdfr_encode_reduce(const float* pred, const float* target, const float* J, i
                        int64_t ws_bytes, double* loss, double* g_zn, int32_t* flags, void* stream);
 int sdfr_encode_step(float* z, float* m, float* v, int L, int B, int unit, const double* g_zn, const double* loss, int32_t* flags, float code_reg,
                      float lr, int t, float* history, int64_t history_stride, void* stream);
+
+/* ---- shape completion from one view (csrc/complete.hip, SDFR_VERSION 419) ----
+ *
+ * A latent fitted to what one sensor position sees of a shape, the decoder frozen.  Every sample row carries an interval [lo, hi] the true
+ * signed distance lies in: lo == hi for an exact sample, [0, s] for a free-space point s in front of its ray's hit.  One iteration is
+ * sdfr_bound_rows -> a decoder forward that saves its masks -> sdfr_mlp_jacobian -> sdfr_bound_reduce -> sdfr_encode_step.  All pointers are
+ * device pointers; no atomics, no memset, no host synchronisation, the same bits on every run.  csrc/complete_cells.h holds the per-element
+ * rules; DESIGN.md 7l.
+ *
+ * sdfr_view_samples: points [N][3] float32 (camera frame), normals [N][3] float64 (camera frame) or NULL, ptoff int64 [B + 1] (shape b owns
+ *   points ptoff[b] .. ptoff[b + 1] - 1), pose [B][6] = cos(yaw), sin(yaw), trans, scale as sdfr_verify_point_rows takes it, origin [3] the
+ *   sensor's position (camera frame, float32).  Point g gives P = 3 + F rows, rows [N P][5] = x y z lo hi, row P g + j for slot j.  With
+ *   x = diag(1, -1, 1) rot_yaw^T (p / scale - trans) in float64 (every operation rounded on its own, the rule of sdfr_verify_point_rows), o the
+ *   origin through the same map and n^ the normal through diag(1, -1, 1) rot_yaw^T divided by its length:
+ *     slot 0      x                       [0, 0]
+ *     slot 1      x + eta n^              [eta, eta]         slots 1 and 2 are invalid without normals, or with a non-finite or zero normal
+ *     slot 2      x - eta n^              [-eta, -eta]
+ *     slot 3 + f  x - s d^                [0, float32(s)]    d^ = (x - o) / r, r = |x - o| = sqrt((dx dx + dy dy) + dz dz),
+ *                                                            s = ((f + u) / F) min(s_max, r); invalid when r is zero or not finite
+ *   u = (mix64(seed ^ mix64(((shape0 + b) << 40 | i << 8 | f) * 0x9E3779B97F4A7C15 + 1)) >> 11) 2^-53 with i = g - ptoff[b] and the mix64 of
+ *   csrc/train_cells.h.  Positions are rounded once to float32; a slot is valid only if its float32 position is finite and in [-1, 1]^3.  An
+ *   invalid slot holds position 0 and lo = hi = NaN, which the reduce leaves out.  eta and s_max are in lattice units (float32, widened to float64 for the
+ *   arithmetic above).  0 <= F <= 64,
+ *   N <= 2^32.  flags int32 [B]: bit 3 (8) ptoff is broken at this shape (ptoff[b] < 0, ptoff[b + 1] < ptoff[b] or ptoff[b + 1] > N) --
+ *   nothing is read through it; bit 2 (4) a non-finite pose word or a scale <= 0.  Every slot of such a shape, and of a point no usable entry
+ *   holds, is invalid.  One point per thread; one launch.
+ *
+ * sdfr_bound_rows: sdfr_encode_rows for samples [S][5] = x y z lo hi: the same table rules, the same draw, the same zn; writes inputs
+ *   [B k][L + 3], lo [B k] and hi [B k].
+ *
+ * sdfr_bound_reduce: sdfr_encode_reduce with the interval rule.  With cp, cl, ch the float32 clamps of p, lo and hi to [-clamp, clamp], over the
+ *   rows with a finite p, lo <= hi and at least one finite bound (n_ok of them; any NaN leaves a row out), in float64:
+ *   d = cp - cl where cp < cl, cp - ch where cp > ch, else 0;  loss[b] = mean |d|;  g_zn[b][c] = mean sgn(d) [-clamp <= p <= clamp] J[i][c].
+ *   A row inside its interval adds nothing but counts in n_ok.  With lo == hi the results are sdfr_encode_reduce's in every bit.  The
+ *   summation order and the workspace (sdfr_encode_ws_bytes) are sdfr_encode_reduce's.  Two launches. */
+int sdfr_view_samples(const float* points, const double* normals, int64_t N, const int64_t* ptoff, int B, const float* pose, const float* origin,
+                      int shape0, int F, float eta, float s_max, int64_t seed, float* rows, int32_t* flags, void* stream);
+int sdfr_bound_rows(const float* samples, int64_t S, const int64_t* soff, int B, int shape0, int64_t k, int draw, int64_t seed, int64_t iter, const float* z,
+                    int L, int unit, float* inputs, float* lo, float* hi, float* zn, int32_t* flags, void* stream);
+int sdfr_bound_reduce(const float* pred, const float* lo, const float* hi, const float* J, int Jstride, int L, int B, int64_t k, float clamp, void* ws,
+                      int64_t ws_bytes, double* loss, double* g_zn, int32_t* flags, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (8 waves * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

@@ -9,7 +9,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDFR_LIB") or os.path.join(_HERE, "lib", "libsdfr_hip.so")     # SDFR_LIB: A/B builds (tools/ab_build.sh)
 
-ABI_VERSION = 418          # include/sdfr.h SDFR_VERSION
+ABI_VERSION = 419          # include/sdfr.h SDFR_VERSION
 _lib = None
 
 # name -> (restype, argtypes); mirrors include/sdfr.h one to one
@@ -257,6 +257,13 @@ _PROTOS = {
                                    c_void_p, c_void_p]),
     "sdfr_encode_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p,
                                  c_int64, c_void_p]),
+    # shape completion from one view: interval sample rows from observed points, the encoder's rows and reduce for them (csrc/complete.hip)
+    "sdfr_view_samples": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int64,
+                                  c_void_p, c_void_p, c_void_p]),
+    "sdfr_bound_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdfr_bound_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_float, c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -1,0 +1,189 @@
+"""Shape completion from one view under a trained shape prior: DeepSDF's other use of a frozen decoder, batched on the device
+(csrc/complete.hip).
+
+    from sdflabel_amd.complete import complete_many, view_samples_many, fit_many, BoundSamples
+
+What a sensor sees of a car is one side of it, and no closed mesh to sign samples with.  A latent can still be fitted to it: to the observed
+points (sdf = 0), to points offset by eta along the surface normal (sdf = +-eta), and to free-space points on the sensor's ray in front of
+each hit, where only an inequality is known.  One generalisation covers the three: every sample row carries an interval [lo, hi] the true
+signed distance lies in.  An exact sample has lo == hi; a free-space point at distance s in front of its ray's hit has [0, s] -- both bounds
+hold for any surface, because the hit itself is s away.  The loss of a row is the distance from the clamped prediction to the clamped
+interval; a row inside its interval adds nothing.  With lo == hi everywhere the fit is encode.encode_many's in every bit.
+
+view_samples_many turns lidar clouds and poses into such rows (sdfr_view_samples), fit_many is encode_many for them (sdfr_bound_rows,
+sdfr_bound_reduce, and encode_many's own decoder launches and Adam step), complete_many chains the two from the parameters the refinement
+leaves.
+
+THE DEFAULTS OF THE ROWS (four free-space rows per point, eta = 0.01, s_max = 0.5, all in lattice units) ARE PARAMETERS WITHOUT A CLAIMED
+OPERATING POINT.  eta is DeepSDF's shape-completion offset only AS RECALLED; it has not been checked against that paper's code, and the
+free-space spacing is ours.  The fit's defaults are encode_many's (see encode.py for what is claimed of them).
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .encode import _fit, _upload
+from .mesh import STAGING_BYTES
+from .sdf_samples import SdfSamples
+
+BAD_POSE, BAD_TABLE = 4, 8                 # view flags (csrc/complete_cells.h)
+MAX_FREE = 64
+
+
+class BoundSamples:
+    """Interval samples of one shape: `.rows` float32 [n][5] = x y z lo hi in the lattice frame, the true signed distance at x y z lying in
+    [lo, hi]; a row whose bounds are NaN is left out of a fit.  `.flags`: the shape's flag word from view_samples_many (a 0-d int32 device
+    tensor: 4 an unusable pose, 8 a broken offset-table entry), else None."""
+
+    def __init__(self, rows, flags=None):
+        self.rows, self.flags = rows, flags
+
+    def __len__(self):
+        return int(self.rows.shape[0])
+
+    def numpy(self):
+        return self.rows.detach().cpu().numpy()
+
+    def save(self, path):
+        """one .npz file with the key `rows`, float32 [n][5].  One host read."""
+        np.savez(path, rows=np.ascontiguousarray(self.numpy(), dtype=np.float32))
+
+    @staticmethod
+    def load(path, device=None):
+        rows = torch.from_numpy(np.asarray(np.load(path)["rows"], np.float32).reshape(-1, 5))
+        return BoundSamples(rows if device is None else rows.to(device))
+
+    @staticmethod
+    def from_sdf(samples):
+        """exact samples as intervals: lo = hi = sdf"""
+        r = samples.rows
+        if r.dim() != 2 or r.shape[1] != 4:
+            raise ValueError("BoundSamples.from_sdf: sample rows must be [n][4] = x y z sdf")
+        return BoundSamples(torch.cat([r, r[:, 3:4]], 1).contiguous())
+
+    @staticmethod
+    def concat(*sets):
+        """the rows of several sets (BoundSamples, or SdfSamples taken through from_sdf) as one; they must share a device"""
+        sets = [BoundSamples.from_sdf(s) if isinstance(s, SdfSamples) else s for s in (sets[0] if len(sets) == 1 and isinstance(sets[0], (list, tuple))
+                                                                                      else sets)]
+        if not sets:
+            raise ValueError("BoundSamples.concat: nothing to join")
+        return BoundSamples(torch.cat([s.rows.reshape(-1, 5) for s in sets]).contiguous())
+
+
+@_lib.traced("view_samples_many")
+def view_samples_many(params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0), free_rows=4, eta=0.01, s_max=0.5, seed=0, _device=None):
+    """Interval sample rows from what one sensor position sees of each shape.
+
+    params_list, clouds: as verify.band_counts takes them -- per annotation the {'yaw', 'trans', 'scale', 'latent'} of the refinement and the
+    camera-frame points [n][3] of its frustum.  normals: per annotation float64 [n][3] camera-frame normals (frame.lidar_normals), or None for
+    no normal rows.  origin: the sensor's position in the camera frame.  Every point p goes to the lattice frame,
+    x = diag(1, -1, 1) rot_yaw^T (p / scale - trans), and gives 3 + free_rows rows: x with [0, 0]; x +- eta n^ with [+-eta, +-eta] (n^ the
+    normal taken to the lattice frame and normalised; left out where it is not finite or zero); and, for f < free_rows,
+    x - s d^ with [0, s], d^ the unit vector from the sensor to x and s = ((f + u) / free_rows) min(s_max, |x - sensor|), u in [0, 1) from
+    the library's hash of (seed, shape, point, f): one stratified draw per slot.  A row whose float32 position leaves [-1, 1]^3 is left out
+    (position 0, NaN bounds).  eta and s_max are in lattice units and are taken as float32; see the module docstring for what the defaults
+    are (eta: DeepSDF's only as recalled).  Returns a list of BoundSamples on the device, views of one array.  No host read and no
+    synchronisation."""
+    params_list, clouds = list(params_list), list(clouds)
+    B, F = len(params_list), int(free_rows)
+    if len(clouds) != B:
+        raise ValueError("view_samples_many: %d parameter sets, %d clouds" % (B, len(clouds)))
+    if normals is not None and len(normals) != B:
+        raise ValueError("view_samples_many: %d parameter sets, %d normal arrays" % (B, len(normals)))
+    if not 0 <= F <= MAX_FREE:
+        raise ValueError("view_samples_many: free_rows must be 0 .. %d (got %d)" % (MAX_FREE, F))
+    if not (np.isfinite(eta) and np.isfinite(s_max) and s_max >= 0):
+        raise ValueError("view_samples_many: eta must be finite, s_max finite and not negative")
+    if B > 65535:
+        raise ValueError("view_samples_many: at most 65535 shapes per call")
+    if B == 0:
+        return []
+    device = _device
+    if device is None:
+        device = next((c.device for c in clouds if torch.is_tensor(c) and c.is_cuda), None)
+        if device is None:
+            device = next((p[k].device for p in params_list for k in ("latent", "trans") if torch.is_tensor(p[k]) and p[k].is_cuda), None)
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise _lib.SdfrError("view_samples_many runs on the GPU only; there is no CPU fallback")
+    from .verify import _pose_rows
+    pts = []
+    for c in clouds:
+        t = c.detach() if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32))
+        t = t.reshape(-1, 3).to(torch.float32)
+        pts.append(t if t.is_cuda else _upload(t, dev))
+    sizes = [int(t.shape[0]) for t in pts]
+    nrm = None
+    if normals is not None:
+        nrm = []
+        for c, n in zip(normals, sizes):
+            t = c.detach() if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float64))
+            t = t.reshape(-1, 3).to(torch.float64)
+            if int(t.shape[0]) != n:
+                raise ValueError("view_samples_many: %d normals for %d points" % (int(t.shape[0]), n))
+            nrm.append(t if t.is_cuda else _upload(t, dev))
+        nrm = torch.cat(nrm).contiguous()
+    ptoff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    N, Pn = int(ptoff[-1]), 3 + F
+    points = torch.cat(pts).contiguous()
+    d_ptoff = _upload(torch.from_numpy(ptoff), dev)
+    pose, _ = _pose_rows(params_list, dev)
+    org = _upload(torch.tensor([float(v) for v in origin], dtype=torch.float32).reshape(3), dev)
+    rows = torch.empty((N * Pn, 5), dtype=torch.float32, device=dev)
+    flags = torch.empty((B,), dtype=torch.int32, device=dev)
+    Pt = _lib.ptr
+    with _lib.guard(dev):
+        _lib.check(_lib.lib().sdfr_view_samples(Pt(points) if N else None, Pt(nrm) if (nrm is not None and N) else None, N, Pt(d_ptoff), B, Pt(pose),
+                                                Pt(org), 0, F, float(eta), float(s_max), int(seed) & 0x7FFFFFFFFFFFFFFF, Pt(rows) if N else None,
+                                                Pt(flags), _lib.stream_ptr()), "sdfr_view_samples")
+    return [BoundSamples(rows[int(ptoff[b]) * Pn:int(ptoff[b + 1]) * Pn], flags[b]) for b in range(B)]
+
+
+@_lib.traced("fit_many")
+def fit_many(dsdf, samples, iters=800, rows_per_iter=8000, lr=5e-3, lr_step=None, lr_factor=0.1, clamp=0.1, code_reg=1e-4, unit_latents=True, init=None,
+             seed=0, history=False, staging_bytes=STAGING_BYTES, draw=None):
+    """encode.encode_many for interval samples: fit one latent per shape to `samples` (a list of BoundSamples, or one) under the frozen
+    decoder.  The keywords, the staging, the random stream and the returned Encoded are encode_many's; the loss of a row is the distance from
+    the clamped prediction to the clamped interval, `.flags` bit 1 (2) means no row with a finite prediction and usable bounds.  On
+    BoundSamples.from_sdf(s) the results are encode_many's on s in every bit."""
+    samples = [samples] if isinstance(samples, BoundSamples) else list(samples)
+    return _fit("fit_many", "sdfr_bound_rows", "sdfr_bound_reduce", 5, "x y z lo hi", dsdf, samples, iters, rows_per_iter, lr, lr_step, lr_factor, clamp,
+                code_reg, unit_latents, init, seed, history, staging_bytes, draw)
+
+
+def _cloud_normals(cloud, radius=1.0, max_nn=30):
+    """frame.lidar_normals of one annotation's cloud among its own points, float64 [n][3] on the device; a point with fewer than 3
+    neighbours gets a NaN normal (lidar_normals' placeholder (0, 0, 1) would be taken for a measurement).  No host synchronisation."""
+    from .frame import lidar_normals
+    n, info = lidar_normals(cloud, radius=radius, max_nn=max_nn, return_info=True)
+    return torch.where((info["nn_count"] < 3)[:, None], torch.full_like(n, float("nan")), n)
+
+
+@_lib.traced("complete_many")
+def complete_many(dsdf, params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0), free_rows=4, eta=0.01, s_max=0.5, seed=0, **fit_kw):
+    """A latent per annotation from its lidar cloud alone: view_samples_many, then fit_many.  params_list gives the pose (and, as the default
+    `init`, the latent the fit starts from); normals=None estimates them with frame.lidar_normals on each cloud (NaN where a
+    point has fewer than 3 neighbours, so its normal rows are left out).  fit_kw: fit_many's keywords.  Returns the Encoded, with the rows
+    as `.samples`."""
+    params_list, clouds = list(params_list), list(clouds)
+    dev = next(dsdf.parameters()).device
+    if dev.type != "cuda":
+        raise _lib.SdfrError("complete_many runs on the GPU only (the decoder is on %s); there is no CPU fallback" % dev)
+    if normals is None:
+        normals = [_cloud_normals(c if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)).to(dev)) if len(c) else
+                   torch.zeros((0, 3), dtype=torch.float64, device=dev) for c in clouds]
+    samples = view_samples_many(params_list, clouds, normals, origin, free_rows, eta, s_max, seed, _device=dev)
+    if fit_kw.get("init") is None and params_list:
+        from .verify import _pose_rows
+        fit_kw["init"] = _pose_rows(params_list, dev)[1]
+    fit_kw.setdefault("seed", seed)
+    enc = fit_many(dsdf, samples, **fit_kw)
+    enc.samples = samples
+    return enc
+
+
+def _latent_cosine(a, b):
+    """float64 [B] on the device: the cosine between the rows of a and b"""
+    a, b = a.double(), b.double()
+    return (torch.nn.functional.normalize(a, dim=1) * torch.nn.functional.normalize(b, dim=1)).sum(1)

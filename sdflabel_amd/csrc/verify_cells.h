@@ -117,15 +117,24 @@ VERIFY_HD void verify_resolve(uint64_t key, uint8_t* mask, float* depth, int32_t
 // pose = cos(yaw), sin(yaw), trans x, y, z, scale (float32; the cosine and sine are the label's own float32 values).  Returns 1 when x lies
 // in [-1, 1]^3 (a NaN does not).
 #define VERIFY_POSE 6
-VERIFY_HD uint8_t verify_point_x(const float* p, const float* pose, float* x) {
+// the float64 part of verify_point_x: x before its one rounding (complete_cells.h offsets it along normals and rays first)
+VERIFY_HD void verify_point_x64(const float* p, const float* pose, double* x) {
     const double c = (double)pose[0], s = (double)pose[1], sc = (double)pose[5];
     const double q0 = (double)p[0] / sc - (double)pose[2];
     const double q1 = (double)p[1] / sc - (double)pose[3];
     const double q2 = (double)p[2] / sc - (double)pose[4];
     const double a0 = c * q0, a1 = s * q2, b0 = s * q0, b1 = c * q2;
-    x[0] = (float)(a0 - a1);
-    x[1] = (float)(-q1);
-    x[2] = (float)(b0 + b1);
+    x[0] = a0 - a1;
+    x[1] = -q1;
+    x[2] = b0 + b1;
+}
+
+VERIFY_HD uint8_t verify_point_x(const float* p, const float* pose, float* x) {
+    double d[3];
+    verify_point_x64(p, pose, d);
+    x[0] = (float)d[0];
+    x[1] = (float)d[1];
+    x[2] = (float)d[2];
     return (uint8_t)(fabsf(x[0]) <= 1.0f && fabsf(x[1]) <= 1.0f && fabsf(x[2]) <= 1.0f);
 }
 

@@ -56,41 +56,50 @@ def encode_many(dsdf, samples, iters=800, rows_per_iter=8000, lr=5e-3, lr_step=N
     False takes the first min(rows_per_iter, smallest count) rows of every shape on every iteration.  Shapes are staged in groups of whole
     shapes whose buffers stay under staging_bytes; the buffers are allocated once.  iters = 0 returns the start.  Returns an Encoded."""
     samples = [samples] if isinstance(samples, SdfSamples) else list(samples)
+    return _fit("encode_many", "sdfr_encode_rows", "sdfr_encode_reduce", 4, "x y z sdf", dsdf, samples, iters, rows_per_iter, lr, lr_step, lr_factor,
+                clamp, code_reg, unit_latents, init, seed, history, staging_bytes, draw)
+
+
+def _fit(who, rows_call, reduce_call, width, layout, dsdf, samples, iters, rows_per_iter, lr, lr_step, lr_factor, clamp, code_reg, unit_latents, init,
+         seed, history, staging_bytes, draw):
+    """The loop of encode_many and complete.fit_many: `samples` have rows of `width` floats, x y z and width - 3 target words; rows_call writes
+    the decoder's inputs and one array per target word, reduce_call takes the decoder's values and those arrays."""
     iters, k_req = int(iters), int(rows_per_iter)
     if iters < 0 or iters >= MAX_ITERS:
-        raise ValueError("encode_many: iters must be 0 .. 2^24 - 1 (got %d)" % iters)
+        raise ValueError("%s: iters must be 0 .. 2^24 - 1 (got %d)" % (who, iters))
     if k_req < 1:
-        raise ValueError("encode_many: rows_per_iter must be at least 1 (got %d)" % k_req)
+        raise ValueError("%s: rows_per_iter must be at least 1 (got %d)" % (who, k_req))
     if not float(clamp) > 0:
-        raise ValueError("encode_many: clamp must be positive")
+        raise ValueError("%s: clamp must be positive" % who)
     B, Ld = len(samples), int(dsdf.latent_size)
     if not 1 <= Ld <= 256:
-        raise ValueError("encode_many: latent sizes 1 .. 256 (the decoder's is %d)" % Ld)
+        raise ValueError("%s: latent sizes 1 .. 256 (the decoder's is %d)" % (who, Ld))
     if B > 65535:
-        raise ValueError("encode_many: at most 65535 shapes per call")
+        raise ValueError("%s: at most 65535 shapes per call" % who)
     if init is not None:
         init = torch.as_tensor(init)
         if init.dim() != 2 or tuple(init.shape) != (B, Ld):
-            raise ValueError("encode_many: init must be [%d][%d] (shapes x the decoder's latent size), got %s" % (B, Ld, tuple(init.shape)))
+            raise ValueError("%s: init must be [%d][%d] (shapes x the decoder's latent size), got %s" % (who, B, Ld, tuple(init.shape)))
     for s in samples:
-        if s.rows.dim() != 2 or s.rows.shape[1] != 4:
-            raise ValueError("encode_many: sample rows must be [n][4] = x y z sdf")
+        if s.rows.dim() != 2 or s.rows.shape[1] != width:
+            raise ValueError("%s: sample rows must be [n][%d] = %s" % (who, width, layout))
     dev = next(dsdf.parameters()).device
     if dev.type != "cuda":
-        raise _lib.SdfrError("encode_many runs on the GPU only (the decoder is on %s); there is no CPU fallback" % dev)
+        raise _lib.SdfrError("%s runs on the GPU only (the decoder is on %s); there is no CPU fallback" % (who, dev))
     for s in samples:
         if not s.rows.is_cuda:
-            raise _lib.SdfrError("encode_many: the sample rows must be on the GPU (SdfSamples.load(path, device))")
+            raise _lib.SdfrError("%s: the sample rows must be on the GPU (%s)" % (who, "SdfSamples.load(path, device)" if width == 4 else
+                                                                                   "BoundSamples.load(path, device)"))
     counts = [len(s) for s in samples]
     full = [c for c in counts if c > 0]
     if draw is None:
         draw = not (full and min(full) == max(full) and full[0] <= k_req)
     k = k_req if draw else min([k_req] + full)
     if k > MAX_ROWS:
-        raise ValueError("encode_many: at most 2^20 rows per shape and iteration")
+        raise ValueError("%s: at most 2^20 rows per shape and iteration" % who)
     lr_step = max(1, iters // 2) if lr_step is None else int(lr_step)
     if lr_step < 1:
-        raise ValueError("encode_many: lr_step must be at least 1")
+        raise ValueError("%s: lr_step must be at least 1" % who)
 
     if init is None:
         z = _upload(torch.randn((B, Ld), generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32) * 0.1, dev)
@@ -104,22 +113,24 @@ def encode_many(dsdf, samples, iters=800, rows_per_iter=8000, lr=5e-3, lr_step=N
         return Encoded(zn, z, loss, flags, hist, bool(unit_latents))
 
     L = _lib.lib()
+    rows_fn, reduce_fn = getattr(L, rows_call), getattr(L, reduce_call)
     P, ck = _lib.ptr, _lib.check
     handle, fwd, f16 = _decoder_mode(dsdf, dev)
-    NI = Ld + 3
-    rows = torch.cat([s.rows for s in samples]).float().contiguous() if sum(counts) else torch.zeros((0, 4), dtype=torch.float32, device=dev)
+    NI, NT = Ld + 3, width - 3
+    rows = torch.cat([s.rows for s in samples]).float().contiguous() if sum(counts) else torch.zeros((0, width), dtype=torch.float32, device=dev)
     S = int(rows.shape[0])
     off = [0]
     for c in counts:
         off.append(off[-1] + c)
     soff = _upload(torch.tensor(off, dtype=torch.int64), dev)
     mask_words = 0 if handle.has_ln else int(L.sdfr_decoder_mask_words(handle.h, k))
-    per_shape = k * (4 * (2 * NI + 3)) + 4 * mask_words
+    per_shape = k * (4 * (2 * NI + 2 + NT)) + 4 * mask_words
     nb = max(1, min(B, int(staging_bytes) // max(per_shape, 1)))
     n_max = nb * k
     inputs = torch.empty((n_max, NI), dtype=torch.float32, device=dev)
     J = torch.empty((n_max, NI), dtype=torch.float32, device=dev)
-    target, pred, sel = (torch.empty((n_max,), dtype=torch.float32, device=dev) for _ in range(3))
+    targets = [torch.empty((n_max,), dtype=torch.float32, device=dev) for _ in range(NT)]
+    pred, sel = (torch.empty((n_max,), dtype=torch.float32, device=dev) for _ in range(2))
     idx = torch.arange(n_max, dtype=torch.int32, device=dev)
     masks = None if handle.has_ln else torch.empty((int(L.sdfr_decoder_mask_words(handle.h, n_max)),), dtype=torch.int32, device=dev)
     ws_bytes = int(L.sdfr_encode_ws_bytes(nb, k, Ld))
@@ -130,23 +141,23 @@ def encode_many(dsdf, samples, iters=800, rows_per_iter=8000, lr=5e-3, lr_step=N
     unit = 1 if unit_latents else 0
     table_flags = torch.empty((nb,), dtype=torch.int32, device=dev)          # the last call's flag output when the loop's flags are kept
     seed64 = int(seed) & 0x7FFFFFFFFFFFFFFF
+    tp, no_t = [P(t) for t in targets], [None] * NT
     with _lib.guard(dev):
         st = _lib.stream_ptr()
         for b0 in range(0, B, nb):
             n = min(nb, B - b0)
             zg, so = z[b0:], soff[b0:]
             for it in range(iters):
-                ck(L.sdfr_encode_rows(P(rows), S, P(so), n, b0, k, 1 if draw else 0, seed64, it, P(zg), Ld, unit, P(inputs), P(target), P(zn[b0:]),
-                                      P(flags[b0:]), st), "sdfr_encode_rows")
+                ck(rows_fn(P(rows), S, P(so), n, b0, k, 1 if draw else 0, seed64, it, P(zg), Ld, unit, P(inputs), *tp, P(zn[b0:]), P(flags[b0:]), st),
+                   rows_call)
                 decoder_rows(handle, fwd, f16, inputs, n * k, pred, J, sel, masks, idx, cnts[n], st)
-                ck(L.sdfr_encode_reduce(P(pred), P(target), P(J), NI, Ld, n, k, float(clamp), P(ws), ws_bytes, P(loss[b0:]), P(g_zn), P(flags[b0:]), st),
-                   "sdfr_encode_reduce")
+                ck(reduce_fn(P(pred), *tp, P(J), NI, Ld, n, k, float(clamp), P(ws), ws_bytes, P(loss[b0:]), P(g_zn), P(flags[b0:]), st), reduce_call)
                 ck(L.sdfr_encode_step(P(zg), P(m[b0:]), P(v[b0:]), Ld, n, unit, P(g_zn), P(loss[b0:]), P(flags[b0:]), float(code_reg),
                                       float(lr) * float(lr_factor) ** (it // lr_step), it + 1, P(hist[:, b0:]) if hist is not None else None, B, st),
                    "sdfr_encode_step")
             # the latents as the decoder sees the final z (and, with iters = 0, the flags of the table)
-            ck(L.sdfr_encode_rows(None, S, P(so), n, b0, k, 0, seed64, 0, P(zg), Ld, unit, None, None, P(zn[b0:]),
-                                  P(flags[b0:] if iters == 0 else table_flags), st), "sdfr_encode_rows")
+            ck(rows_fn(None, S, P(so), n, b0, k, 0, seed64, 0, P(zg), Ld, unit, None, *no_t, P(zn[b0:]),
+                       P(flags[b0:] if iters == 0 else table_flags), st), rows_call)
     return Encoded(zn, z, loss, flags, hist, bool(unit_latents))
 
 

@@ -21,6 +21,7 @@ from ..frame import (NECESSARY_KEYS, _as_tensor, css_inputs_many, depth_map, fra
 from ..export import crops_many
 from ..mesh import meshes_many
 from .. import verify as _verify
+from ..complete import _latent_cosine, complete_many
 from ..verify import label_windows, verify_many
 from .optimizer import optimize_many
 from .pose import PoseEstimator
@@ -53,7 +54,8 @@ def _stage_size(kw, boxes):
 
 
 def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, iters, weights, pose_type='kabsch', scale=2.0, rendering_area=32,
-                 sampler='device', seed=0, keys=None, optimize_kwargs=None, return_stages=False, mesh_resolution=None, verify=None, crops=None):
+                 sampler='device', seed=0, keys=None, optimize_kwargs=None, return_stages=False, mesh_resolution=None, verify=None, crops=None,
+                 complete=None):
     """One frame from crops to the evaluator's dict.
 
     annotations: per annotation a dict with 'bbox' [l, t, r, b] (the crop's box in the image), 'color' (the crop of the image, (H, W, 3)),
@@ -83,8 +85,17 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
     frame's K) and `.extrinsics` (the label's cam_T); pipelines.export_crops.export_frame writes them.  No host read; est, kept and every
     other stage are the bits of the call without crops.  None: nothing changes.
     With verify and crops both on and agreeing on image size, margin and z_min, the frame is rasterised once: one verify.RasterBatch goes to
-    both stages.  Their results are the bits of the separate calls."""
+    both stages.  Their results are the bits of the separate calls.
+    complete (needs return_stages=True): True, or a dict of complete.complete_many's keyword arguments.  The stages gain 'complete' =
+    {'encoded', 'cosine'}: a latent per entry of stages['params'] fitted to its lidar cloud alone (stages['lidar'][i][0]) at the refined pose, starting
+    from the refined latent -- an independent check of the refinement beside verify --, and float64 [n] on the device, the cosine between the
+    completed and the refined unit latents.  `origin`, the sensor's position, is the camera centre by default: that approximates the KITTI
+    lidar's own position, which sits some decimetres from the camera.  No host read; est, kept and every other stage are the bits of the call
+    without complete.  None: nothing changes."""
     mesh_resolution, verify, crops = _stage_options("refine_frame", return_stages, mesh_resolution, verify, crops)
+    complete = None if complete is None or complete is False else ({} if complete is True else dict(complete))
+    if complete is not None and not return_stages:
+        raise ValueError("refine_frame: complete needs return_stages=True (the completed latents are returned among the stages)")
     device = grid.points.device
     precision = grid.points.dtype
     n = len(annotations)
@@ -132,6 +143,11 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
         crop_list = crops_many(meshes, K_orig, boxes, csize, colors=[annotations[kept[j]]['color'] for j in live], raster=shared, **ckw)
         for c, j in zip(crop_list, live):
             c.latent, c.intrinsics, c.extrinsics = refined[j]['latent'], K_orig, labels[j][2]
+    completed = None
+    if complete is not None:
+        enc = complete_many(dsdf, refined, [lidar[i][0] for i in kept], **complete)
+        ref_lat = torch.stack([torch.as_tensor(r['latent']).detach().reshape(-1).to(enc.latents.device) for r in refined]) if refined else enc.latents
+        completed = {'encoded': enc, 'cosine': _latent_cosine(enc.latents, ref_lat)}
     kept = [i for i, lab in zip(kept, labels) if lab is not None]
     if return_stages:
         stages = {'crop_sizes': sizes, 'intrinsics': intr, 'off_intrinsics': off, 'lidar': lidar, 'nocs_3d': nocs3d, 'surfaces': surf,
@@ -142,13 +158,16 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
             stages['verify'] = verdicts
         if crop_list is not None:
             stages['crops'] = crop_list
+        if completed is not None:
+            stages['complete'] = completed
         return est, kept, stages
     return est, kept
 
 
 def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_annos='', label_type='gt', maskrcnn_labels=None, lidar=None,
                   css_batch=None, pose_type='kabsch', scale=2.0, rendering_area=32, sampler='device', seed=0, keys=None, optimize_kwargs=None,
-                  return_stages=False, remove_road=False, mesh_resolution=None, verify=None, crops=None):
+                  return_stages=False, remove_road=False, mesh_resolution=None, verify=None, crops=None,
+                  complete=None):
     """One KITTI sample from the loaded frame to the evaluator's dicts: the body of the reference's frame loop (refine_css.py:94-245).
 
     sample: {'image' (H, W, 3) float32 BGR in 0 ... 1, 'orig_cam' 3x3, 'world_to_cam' 4x4, 'annos' {'easy', 'medium', 'hard'} and 'depth'
@@ -186,7 +205,9 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
     verify: refine_frame's (needs return_stages=True; the stages gain 'verify').  The windows are clipped to the sample's image, and with
     label_type='maskrcnn' the matched detector masks are the label masks, so 'iou_mask' is filled.
     crops: refine_frame's (needs return_stages=True; the stages gain 'crops').  The windows are clipped to the sample's image and the RGB
-    bytes come from the sample's image."""
+    bytes come from the sample's image.
+    complete: refine_frame's (needs return_stages=True; the stages gain 'complete').  The sensor's position defaults to the camera centre,
+    an approximation of the KITTI lidar's own position."""
     mesh_resolution, verify, crops = _stage_options("refine_sample", return_stages, mesh_resolution, verify, crops)
     if label_type not in ('gt', 'rcnn', 'maskrcnn'):
         raise ValueError("refine_sample: label_type must be 'gt', 'rcnn' or 'maskrcnn'")
@@ -260,7 +281,7 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
         crops = dict(crops, image_size=(W, H))
     out = refine_frame(annotations, dsdf, grid, latents, K_orig, sample['world_to_cam'], iters, weights, pose_type=pose_type, scale=scale,
                        rendering_area=rendering_area, sampler=sampler, seed=seed, keys=None if keys is None else [keys[i] for i in live],
-                       optimize_kwargs=optimize_kwargs, return_stages=return_stages, mesh_resolution=mesh_resolution, verify=verify, crops=crops)
+                       optimize_kwargs=optimize_kwargs, return_stages=return_stages, mesh_resolution=mesh_resolution, verify=verify, crops=crops, complete=complete)
     kept = [live[j] for j in out[1]]
     if return_stages:
         stages = dict(out[2], annos=annos, boxes=boxes, match=match, css_input=css_in, css_input_orig=css_vis, nocs_pred=nocs, latents=latents,
