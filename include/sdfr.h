@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 419        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 420        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -49,7 +49,7 @@ extern "C" {
  * grid forward's launch order from the last pass, sdfr_mlp_balance_* and sdfr_mlp_forward_balanced, and the per-workgroup tile trace of trace
  * builds, sdfr_debug_set_tile_trace; 417: training the decoder, sdfr_decoder_train_*; 418: encoding shapes under a
  * frozen decoder, sdfr_encode_*; 419: shape completion from one view, sdfr_view_samples and
- * sdfr_bound_*).  A caller built
+ * sdfr_bound_*; 420: pose and shape fitted to one view, sdfr_align_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -1243,6 +1243,58 @@ int sdfr_bound_rows(const float* samples, int64_t S, const int64_t* soff, int B,
                     int L, int unit, float* inputs, float* lo, float* hi, float* zn, int32_t* flags, void* stream);
 int sdfr_bound_reduce(const float* pred, const float* lo, const float* hi, const float* J, int Jstride, int L, int B, int64_t k, float clamp, void* ws,
                       int64_t ws_bytes, double* loss, double* g_zn, int32_t* flags, void* stream);
+
+/* ---- pose and shape fitted to one view (csrc/align.hip, SDFR_VERSION 420) ----
+ *
+ * The interval fit of the completion with the pose free: yaw, trans and scale move with the latent, the decoder frozen.  The observation rows
+ * are made once, in the CAMERA frame and in METRES, so they hold whatever the pose becomes.  One iteration is  sdfr_align_rows -> a decoder
+ * forward that saves its masks -> sdfr_mlp_jacobian (its last three columns are d sdf / d xyz) -> sdfr_align_reduce -> sdfr_align_step.  All
+ * pointers are device pointers (but lr_pose, five floats of the host read before the launch, like lr); no atomics, no memset, no host
+ * synchronisation, the same bits on every run, and a shape's results do not depend on B or on its position in the batch.  Float64 and
+ * float32 operations are rounded one by one.  csrc/align_cells.h holds the per-element rules; DESIGN.md 7m.
+ *
+ *   pose [B][6] = cos(yaw), sin(yaw), trans, scale (the row of sdfr_verify_point_rows); theta [B][5] = yaw, trans, scale, the variables.
+ *   flags[b]    the bits of sdfr_encode_rows / _reduce / _step, and bit 4 (16): pose[b] holds a non-finite word or a scale <= 0.
+ *
+ * sdfr_align_samples: sdfr_view_samples without a pose.  Point g (float32, camera frame) with normal n (float64, camera frame, or NULL) gives
+ *   P = 3 + F rows [N P][5] = q lo hi, q the float64 position rounded once, [lo, hi] an interval the true METRIC signed distance at q lies in:
+ *     slot 0      p                [0, 0]
+ *     slot 1      p + eta n^       [eta, eta]          n^ = n / sqrt((n0 n0 + n1 n1) + n2 n2); invalid without a finite non-zero normal
+ *     slot 2      p - eta n^       [-eta, -eta]
+ *     slot 3 + f  p - s d^         [0, float32(s)]     d^ = (p - o) / r, s = ((f + u) / F) min(s_max, r); invalid when r is zero or not finite
+ *   u: the hash of sdfr_view_samples.  eta and s_max are in metres.  A slot is valid only if its point is finite; an invalid slot holds position
+ *   0 and NaN bounds; there is no cube test.  flags int32 [B]: bit 3 (8) ptoff is broken at this shape; nothing is read through it.
+ *
+ * sdfr_align_rows: sdfr_bound_rows (the same table rules, draw and zn) on those rows, with pose [B][6]: for the drawn sample (q, lo, hi) it
+ *   writes inputs [B k][L + 3] = (zn[b], float32(x)) with x = diag(1, -1, 1) rot_yaw^T (q / scale - trans) in float64 (the operations of
+ *   sdfr_verify_point_rows), cam [B k][3] = q, lo and hi [B k].  A row whose float32 x leaves [-1, 1]^3 gets x = 0 and NaN bounds for this
+ *   iteration.  An unusable pose makes every row of its shape so and raises bit 4.  inputs == NULL: zn and flags only.
+ *
+ * sdfr_align_reduce: with pm = float32(scale p) the row rule is sdfr_bound_reduce's on (pm, lo, hi, clamp), clamp in metres.  Per shape over
+ *   the ok rows, in float64: loss[b] = mean e;  g[b][0 .. L + 4] = mean w d pm / d (zn, yaw, tx, ty, tz, scale), with (gx, gy, gz) =
+ *   J[L .. L + 2], c, sn = pose[0], pose[1], x recomputed in float64 from cam and pose:
+ *     zn_i   scale J[i]                          yaw    scale (gz x0 - gx x2)
+ *     tx     -(scale (gx c + gz sn))             ty     scale gy                 tz    scale (gx sn - gz c)
+ *     scale  p + scale ((gx (c u0 - sn u2) - gy u1) + gz (sn u0 + c u2)),  u = -(q / (scale scale))
+ *   each operation as written, one rounding each.  The summation order is sdfr_encode_reduce's (the same kernels).  J has Jstride >= L + 3
+ *   words a row.  ws: sdfr_align_ws_bytes(B, k, L) bytes, aligned to 8.  At scale == 1 loss and the L latent columns are sdfr_bound_reduce's
+ *   in every bit.  Two launches.
+ *
+ * sdfr_align_step: the latent by sdfr_encode_step's rule with rate lr, and the same Adam on theta with state tm, tv [B][5] and rates
+ *   lr_pose[5]; a rate of 0 (lr included) leaves its parameter and state untouched.  A shape whose flags hold bit 0, 1, 3 or 4, whose
+ *   gradient has a non-finite element (all L + 5, as float32), or whose stepped scale would not be finite and positive keeps everything and
+ *   gets bit 2.  A stepped shape gets its next pose row: float32(cos(double(yaw))), float32(sin(double(yaw))), trans, scale.  history as
+ *   sdfr_encode_step's. */
+int sdfr_align_samples(const float* points, const double* normals, int64_t N, const int64_t* ptoff, int B, const float* origin, int shape0, int F,
+                       float eta, float s_max, int64_t seed, float* rows, int32_t* flags, void* stream);
+int sdfr_align_rows(const float* samples, int64_t S, const int64_t* soff, int B, int shape0, int64_t k, int draw, int64_t seed, int64_t iter, const float* z,
+                    int L, int unit, const float* pose, float* inputs, float* cam, float* lo, float* hi, float* zn, int32_t* flags, void* stream);
+int64_t sdfr_align_ws_bytes(int B, int64_t k, int L);
+int sdfr_align_reduce(const float* pred, const float* lo, const float* hi, const float* J, int Jstride, const float* cam, const float* pose, int L, int B,
+                      int64_t k, float clamp, void* ws, int64_t ws_bytes, double* loss, double* g, int32_t* flags, void* stream);
+int sdfr_align_step(float* z, float* m, float* v, int L, int B, int unit, float* theta, float* tm, float* tv, float* pose, const double* g,
+                    const double* loss, int32_t* flags, float code_reg, float lr, const float* lr_pose, int t, float* history, int64_t history_stride,
+                    void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (8 waves * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

@@ -9,7 +9,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDFR_LIB") or os.path.join(_HERE, "lib", "libsdfr_hip.so")     # SDFR_LIB: A/B builds (tools/ab_build.sh)
 
-ABI_VERSION = 419          # include/sdfr.h SDFR_VERSION
+ABI_VERSION = 420          # include/sdfr.h SDFR_VERSION
 _lib = None
 
 # name -> (restype, argtypes); mirrors include/sdfr.h one to one
@@ -264,6 +264,17 @@ _PROTOS = {
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdfr_bound_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_float, c_void_p, c_int64, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    # pose and shape fitted to one view: camera-frame interval rows, the iteration's rows through a pose, the loss and the gradient with
+    # respect to latent, yaw, trans and scale, Adam on both (csrc/align.hip)
+    "sdfr_align_samples": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float, c_int64, c_void_p,
+                                   c_void_p, c_void_p]),
+    "sdfr_align_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdfr_align_ws_bytes": (c_int64, [c_int, c_int64, c_int]),
+    "sdfr_align_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int64, c_float, c_void_p, c_int64,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdfr_align_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_float, c_float, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

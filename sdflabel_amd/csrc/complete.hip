@@ -45,7 +45,7 @@ extern "C" int sdfr_bound_rows(const float* samples, int64_t S, const int64_t* s
 
 struct CplBoundRule {
     const float *lo, *hi;
-    __device__ EncRow operator()(float p, int64_t i, float clamp) const { return cpl_row(p, lo[i], hi[i], clamp); }
+    __device__ EncRow operator()(float p, int64_t i, int, float clamp) const { return cpl_row(p, lo[i], hi[i], clamp); }
 };
 
 extern "C" int sdfr_bound_reduce(const float* pred, const float* lo, const float* hi, const float* J, int Jstride, int L, int B, int64_t k, float clamp,

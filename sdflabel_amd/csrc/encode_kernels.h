@@ -1,11 +1,13 @@
-// The kernels the latent fits share (encode.hip: exact targets; complete.hip: interval targets): the iteration's rows for samples of W
-// floats, and THE ONE COPY of the reduce -- the chunk kernel over a row rule and the fold -- whose summation order is encode_cells.h's.
+// The kernels the frozen-decoder fits share (encode.hip: exact targets; complete.hip: interval targets; align.hip: interval targets and a
+// pose): the iteration's rows for samples of W floats, and THE ONE COPY of the reduce -- the chunk kernel over a row rule and a column rule,
+// and the fold -- whose summation order is encode_cells.h's.
 // Device code only; a translation unit that includes it is compiled with -ffp-contract=off.
 #pragma once
 #include "sdfr_common.h"
 #include "encode_cells.h"
 
 #define ENC_THREADS 256
+#define ENC_MAX_G (ENC_MAX_L + 5)          // gradient columns of a reduce at the most: the latent's and the five of a pose (align.hip)
 
 // grid (ceil(k / 256), B) -- or (1, B) without inputs: zn and flags only.  A workgroup writes 256 rows of one shape: the sample of each row
 // goes to LDS first, then the [256][L + 3] block is written element by element (consecutive threads, consecutive words).  Samples are
@@ -71,19 +73,32 @@ static int enc_rows_launch(const char* name, const float* samples, int64_t S, co
 }
 
 // ---- reduce ---------------------------------------------------------------------------------------------------------------------------------
-// A row rule gives the EncRow of row i (an index into the [B k] arrays) from its prediction: the exact rule reads one target, the interval
-// rule two bounds.
+// A row rule gives the EncRow of row i (an index into the [B k] arrays) of shape b from its prediction: the exact rule reads one target, the
+// interval rule two bounds.  A column rule gives the value of column c < G + 2 of that row (G gradient columns, then the loss and the count
+// of ok rows): the latent fits take the latent columns of J (enc_value, G = L), the pose-and-shape fit of align.hip adds the pose's.
 struct EncExactRule {
     const float* target;
-    __device__ EncRow operator()(float p, int64_t i, float clamp) const { return enc_row(p, target[i], clamp); }
+    __device__ EncRow operator()(float p, int64_t i, int, float clamp) const { return enc_row(p, target[i], clamp); }
 };
 
-// grid (chunks, B): one workgroup sums one chunk of ENC_CHUNK rows of one shape into part[b][chunk][L + 2], in the order of encode_cells.h.
+// A column rule may keep EXTRA float64 words a row in LDS, written once per row (prepare) before the columns are summed: values that are
+// costly and shared by no other row.  What is summed, and in which order, does not depend on where a value was formed.
+struct EncLatentCols {
+    static constexpr int EXTRA = 0;
+    const float* J;
+    int Jstride;
+    __device__ void prepare(double*, float, int64_t, int) const {}
+    __device__ double operator()(int c, int G, float w, double e, int ok, int64_t i, int, const double*) const {
+        return enc_value(c, G, w, e, ok, J + i * Jstride);
+    }
+};
+
+// grid (chunks, B): one workgroup sums one chunk of ENC_CHUNK rows of one shape into part[b][chunk][G + 2], in the order of encode_cells.h.
 // The rows' weights go to LDS once; then, ENC_COLS columns at a time, accumulator (slot j, column c) belongs to thread j ncols + c, so the
 // threads of a wave read consecutive words of a row of J.
-template <class Rule>
-__global__ __launch_bounds__(ENC_THREADS) void enc_chunk_kernel(const float* __restrict__ pred, Rule rule, const float* __restrict__ J, int Jstride, int L,
-                                                               int64_t k, float clamp, double* __restrict__ part) {
+template <class Rule, class Cols>
+__global__ __launch_bounds__(ENC_THREADS) void enc_chunk_kernel(const float* __restrict__ pred, Rule rule, Cols cols, int G, int64_t k, float clamp,
+                                                               double* __restrict__ part) {
     const int b = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x;
     const int64_t chunks = gridDim.x;
     const int64_t row0 = (int64_t)ch * ENC_CHUNK;
@@ -93,19 +108,21 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_chunk_kernel(const float* __r
     __shared__ float s_w[ENC_CHUNK];
     __shared__ unsigned char s_ok[ENC_CHUNK];
     __shared__ double s_acc[ENC_SLOTS * (ENC_COLS + 1)];
+    __shared__ double s_x[Cols::EXTRA ? ENC_CHUNK * Cols::EXTRA : 1];
     for (int r = tid; r < n; r += ENC_THREADS) {
-        const EncRow q = rule(pred[base + r], base + r, clamp);
+        const EncRow q = rule(pred[base + r], base + r, b, clamp);
         s_e[r] = q.e; s_w[r] = q.w; s_ok[r] = (unsigned char)q.ok;
+        cols.prepare(s_x + r * Cols::EXTRA, q.w, base + r, b);
     }
     __syncthreads();
-    const int NC = L + 2;
+    const int NC = G + 2;
     double* out = part + ((int64_t)b * chunks + ch) * NC;
     for (int c0 = 0; c0 < NC; c0 += ENC_COLS) {
         const int nc = (NC - c0) < ENC_COLS ? (NC - c0) : ENC_COLS;
         for (int e = tid; e < ENC_SLOTS * nc; e += ENC_THREADS) {
             const int j = e / nc, c = c0 + (e - j * nc);
             double a = 0.0;
-            ENC_SLOT_ROWS(r, j, n) a += enc_value(c, L, s_w[r], s_e[r], s_ok[r], J + (base + r) * Jstride);
+            ENC_SLOT_ROWS(r, j, n) a += cols(c, G, s_w[r], s_e[r], s_ok[r], base + r, b, s_x + r * Cols::EXTRA);
             s_acc[j * (ENC_COLS + 1) + (c - c0)] = a;
         }
         __syncthreads();
@@ -122,47 +139,58 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_chunk_kernel(const float* __r
 }
 
 // grid (B): the chunk sums in chunk order, the means, bit 1 of the flags
-static __global__ __launch_bounds__(64) void enc_fold_kernel(const double* __restrict__ part, int64_t chunks, int L, double* __restrict__ loss,
+static __global__ __launch_bounds__(64) void enc_fold_kernel(const double* __restrict__ part, int64_t chunks, int G, double* __restrict__ loss,
                                                             double* __restrict__ g_zn, int32_t* __restrict__ flags) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int NC = L + 2;
-    __shared__ double s_tot[ENC_MAX_L + 2];
+    const int NC = G + 2;
+    __shared__ double s_tot[ENC_MAX_G + 2];
     for (int c = tid; c < NC; c += 64) {
         double a = 0.0;
         for (int64_t ch = 0; ch < chunks; ++ch) a += part[((int64_t)b * chunks + ch) * NC + c];
         s_tot[c] = a;
     }
     __syncthreads();
-    const double n_ok = s_tot[L + 1];
-    for (int c = tid; c < L; c += 64) g_zn[(int64_t)b * L + c] = enc_mean(s_tot[c], n_ok);
+    const double n_ok = s_tot[G + 1];
+    for (int c = tid; c < G; c += 64) g_zn[(int64_t)b * G + c] = enc_mean(s_tot[c], n_ok);
     if (tid == 0) {
-        loss[b] = enc_mean(s_tot[L], n_ok);
+        loss[b] = enc_mean(s_tot[G], n_ok);
         if (!(n_ok > 0.0)) flags[b] |= ENC_NO_ROWS;
     }
 }
 
-static inline int64_t enc_ws_bytes(int B, int64_t k, int L) {
+// bytes of the partial sums of a reduce with `extra` gradient columns beyond the latent's (0: the latent fits; -1: sizes the kernels refuse)
+static inline int64_t enc_ws_bytes(int B, int64_t k, int L, int extra = 0) {
     if (B < 0 || B > ENC_MAX_B || k < 1 || k > ENC_MAX_K || L < 1 || L > ENC_MAX_L) return -1;
-    return (int64_t)B * enc_chunks(k) * (L + 2) * (int64_t)sizeof(double);
+    return (int64_t)B * enc_chunks(k) * (L + extra + 2) * (int64_t)sizeof(double);
 }
 
-// the argument checks and the two launches of a reduce; `targets_ok`: the rule's own pointers are not NULL
-template <class Rule>
-static int enc_reduce_launch(const char* name, const float* pred, Rule rule, bool targets_ok, const float* J, int Jstride, int L, int B, int64_t k,
-                             float clamp, void* ws, int64_t ws_bytes, double* loss, double* g_zn, int32_t* flags, void* stream) {
-    SDFR_REQUIRE(pred && targets_ok && J && ws && loss && g_zn && flags, "%s: NULL argument", name);
-    SDFR_REQUIRE(L >= 1 && L <= ENC_MAX_L && Jstride >= L, "%s: latent size %d outside [1,%d] or beyond the row stride %d", name, L, ENC_MAX_L, Jstride);
+// the argument checks and the two launches of a reduce over G = L + extra gradient columns; `targets_ok`: the rules' own pointers are not
+// NULL; J has at least `need` words a row; `ws_name` is the entry point that gives the workspace's size
+template <class Rule, class Cols>
+static int enc_reduce_launch(const char* name, const char* ws_name, const float* pred, Rule rule, Cols cols, bool targets_ok, const float* J, int Jstride,
+                             int need, int L, int extra, int B, int64_t k, float clamp, void* ws, int64_t ws_bytes, double* loss, double* g,
+                             int32_t* flags, void* stream) {
+    SDFR_REQUIRE(pred && targets_ok && J && ws && loss && g && flags, "%s: NULL argument", name);
+    SDFR_REQUIRE(L >= 1 && L <= ENC_MAX_L && Jstride >= need, "%s: latent size %d outside [1,%d] or beyond the row stride %d", name, L, ENC_MAX_L, Jstride);
     SDFR_REQUIRE(B >= 0 && B <= ENC_MAX_B && k >= 1 && k <= ENC_MAX_K, "%s: bad size (B = %d, k = %lld)", name, B, (long long)k);
     SDFR_REQUIRE(clamp > 0.f, "%s: clamp must be positive", name);
-    SDFR_REQUIRE(ws_bytes >= enc_ws_bytes(B, k, L), "%s: the workspace holds %lld bytes, sdfr_encode_ws_bytes asks for %lld", name, (long long)ws_bytes,
-                 (long long)enc_ws_bytes(B, k, L));
+    SDFR_REQUIRE(ws_bytes >= enc_ws_bytes(B, k, L, extra), "%s: the workspace holds %lld bytes, %s asks for %lld", name, (long long)ws_bytes, ws_name,
+                 (long long)enc_ws_bytes(B, k, L, extra));
     SDFR_REQUIRE(((uintptr_t)ws & 7) == 0, "%s: the workspace must be aligned to 8 bytes", name);
     if (B == 0) return SDFR_OK;
     const int64_t chunks = enc_chunks(k);
-    hipLaunchKernelGGL(enc_chunk_kernel<Rule>, dim3((unsigned)chunks, B), dim3(ENC_THREADS), 0, (hipStream_t)stream, pred, rule, J, Jstride, L, k, clamp,
-                       (double*)ws);
+    hipLaunchKernelGGL((enc_chunk_kernel<Rule, Cols>), dim3((unsigned)chunks, B), dim3(ENC_THREADS), 0, (hipStream_t)stream, pred, rule, cols, L + extra, k,
+                       clamp, (double*)ws);
     SDFR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(enc_fold_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const double*)ws, chunks, L, loss, g_zn, flags);
+    hipLaunchKernelGGL(enc_fold_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const double*)ws, chunks, L + extra, loss, g, flags);
     SDFR_LAUNCH_CHECK();
     return SDFR_OK;
+}
+
+// the latent fits' reduce: the latent columns of J
+template <class Rule>
+static int enc_reduce_launch(const char* name, const float* pred, Rule rule, bool targets_ok, const float* J, int Jstride, int L, int B, int64_t k,
+                             float clamp, void* ws, int64_t ws_bytes, double* loss, double* g_zn, int32_t* flags, void* stream) {
+    return enc_reduce_launch(name, "sdfr_encode_ws_bytes", pred, rule, EncLatentCols{J, Jstride}, targets_ok, J, Jstride, L, L, 0, B, k, clamp, ws, ws_bytes,
+                             loss, g_zn, flags, stream);
 }

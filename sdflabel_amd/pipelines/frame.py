@@ -22,6 +22,7 @@ from ..export import crops_many
 from ..mesh import meshes_many
 from .. import verify as _verify
 from ..complete import _latent_cosine, complete_many
+from ..align import align_many
 from ..verify import label_windows, verify_many
 from .optimizer import optimize_many
 from .pose import PoseEstimator
@@ -55,7 +56,7 @@ def _stage_size(kw, boxes):
 
 def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, iters, weights, pose_type='kabsch', scale=2.0, rendering_area=32,
                  sampler='device', seed=0, keys=None, optimize_kwargs=None, return_stages=False, mesh_resolution=None, verify=None, crops=None,
-                 complete=None):
+                 complete=None, align=None):
     """One frame from crops to the evaluator's dict.
 
     annotations: per annotation a dict with 'bbox' [l, t, r, b] (the crop's box in the image), 'color' (the crop of the image, (H, W, 3)),
@@ -91,8 +92,16 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
     from the refined latent -- an independent check of the refinement beside verify --, and float64 [n] on the device, the cosine between the
     completed and the refined unit latents.  `origin`, the sensor's position, is the camera centre by default: that approximates the KITTI
     lidar's own position, which sits some decimetres from the camera.  No host read; est, kept and every other stage are the bits of the call
-    without complete.  None: nothing changes."""
+    without complete.  None: nothing changes.
+    align (needs return_stages=True): True, or a dict of align.align_many's keyword arguments.  The stages gain 'align' = {'aligned', 'delta'}:
+    pose and shape of every entry of stages['params'] fitted to its lidar cloud alone (stages['lidar'][i][0]), starting from the refined
+    parameters -- a second, independent estimate of the pose, not only of the latent --, and float32 [n][5] on the device, the fitted yaw,
+    trans and scale minus the refined ones.  `origin` as for complete.  No host read; est, kept and every other stage are the bits of the call
+    without align.  None: nothing changes."""
     mesh_resolution, verify, crops = _stage_options("refine_frame", return_stages, mesh_resolution, verify, crops)
+    align = None if align is None or align is False else ({} if align is True else dict(align))
+    if align is not None and not return_stages:
+        raise ValueError("refine_frame: align needs return_stages=True (the fitted poses are returned among the stages)")
     complete = None if complete is None or complete is False else ({} if complete is True else dict(complete))
     if complete is not None and not return_stages:
         raise ValueError("refine_frame: complete needs return_stages=True (the completed latents are returned among the stages)")
@@ -148,6 +157,12 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
         enc = complete_many(dsdf, refined, [lidar[i][0] for i in kept], **complete)
         ref_lat = torch.stack([torch.as_tensor(r['latent']).detach().reshape(-1).to(enc.latents.device) for r in refined]) if refined else enc.latents
         completed = {'encoded': enc, 'cosine': _latent_cosine(enc.latents, ref_lat)}
+    aligned = None
+    if align is not None:
+        fitted = align_many(dsdf, refined, [lidar[i][0] for i in kept], **align)
+        start = torch.stack([torch.cat([torch.as_tensor(r[key]).detach().reshape(-1)[:n_].to(fitted.theta.device, torch.float32)
+                                        for key, n_ in (('yaw', 1), ('trans', 3), ('scale', 1))]) for r in refined]) if refined else fitted.theta
+        aligned = {'aligned': fitted, 'delta': fitted.theta - start}
     kept = [i for i, lab in zip(kept, labels) if lab is not None]
     if return_stages:
         stages = {'crop_sizes': sizes, 'intrinsics': intr, 'off_intrinsics': off, 'lidar': lidar, 'nocs_3d': nocs3d, 'surfaces': surf,
@@ -160,6 +175,8 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
             stages['crops'] = crop_list
         if completed is not None:
             stages['complete'] = completed
+        if aligned is not None:
+            stages['align'] = aligned
         return est, kept, stages
     return est, kept
 
@@ -167,7 +184,7 @@ def refine_frame(annotations, dsdf, grid, css_latents, K_orig, world_to_cam, ite
 def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_annos='', label_type='gt', maskrcnn_labels=None, lidar=None,
                   css_batch=None, pose_type='kabsch', scale=2.0, rendering_area=32, sampler='device', seed=0, keys=None, optimize_kwargs=None,
                   return_stages=False, remove_road=False, mesh_resolution=None, verify=None, crops=None,
-                  complete=None):
+                  complete=None, align=None):
     """One KITTI sample from the loaded frame to the evaluator's dicts: the body of the reference's frame loop (refine_css.py:94-245).
 
     sample: {'image' (H, W, 3) float32 BGR in 0 ... 1, 'orig_cam' 3x3, 'world_to_cam' 4x4, 'annos' {'easy', 'medium', 'hard'} and 'depth'
@@ -207,7 +224,8 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
     crops: refine_frame's (needs return_stages=True; the stages gain 'crops').  The windows are clipped to the sample's image and the RGB
     bytes come from the sample's image.
     complete: refine_frame's (needs return_stages=True; the stages gain 'complete').  The sensor's position defaults to the camera centre,
-    an approximation of the KITTI lidar's own position."""
+    an approximation of the KITTI lidar's own position.
+    align: refine_frame's (needs return_stages=True; the stages gain 'align')."""
     mesh_resolution, verify, crops = _stage_options("refine_sample", return_stages, mesh_resolution, verify, crops)
     if label_type not in ('gt', 'rcnn', 'maskrcnn'):
         raise ValueError("refine_sample: label_type must be 'gt', 'rcnn' or 'maskrcnn'")
@@ -281,7 +299,8 @@ def refine_sample(sample, css_net, dsdf, grid, iters, weights, annos=None, diff_
         crops = dict(crops, image_size=(W, H))
     out = refine_frame(annotations, dsdf, grid, latents, K_orig, sample['world_to_cam'], iters, weights, pose_type=pose_type, scale=scale,
                        rendering_area=rendering_area, sampler=sampler, seed=seed, keys=None if keys is None else [keys[i] for i in live],
-                       optimize_kwargs=optimize_kwargs, return_stages=return_stages, mesh_resolution=mesh_resolution, verify=verify, crops=crops, complete=complete)
+                       optimize_kwargs=optimize_kwargs, return_stages=return_stages, mesh_resolution=mesh_resolution, verify=verify, crops=crops, complete=complete,
+                       align=align)
     kept = [live[j] for j in out[1]]
     if return_stages:
         stages = dict(out[2], annos=annos, boxes=boxes, match=match, css_input=css_in, css_input_orig=css_vis, nocs_pred=nocs, latents=latents,
