@@ -21,9 +21,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .complete import MAX_FREE, BoundSamples, _cloud_normals
-from .encode import MAX_ITERS, MAX_ROWS, _upload
-from .mesh import STAGING_BYTES, _decoder_mode, decoder_rows
+from .complete import BoundSamples, _check_view, _cloud_normals, _on_device, _view_rows
+from .encode import _Fit, _fit, _upload
+from .mesh import STAGING_BYTES
 
 EMPTY, NO_ROWS, SKIPPED, BAD_TABLE, BAD_POSE = 1, 2, 4, 8, 16            # Aligned.flags (csrc/encode_cells.h, csrc/align_cells.h)
 POSE_KEYS = ("yaw", "tx", "ty", "tz", "scale")                           # the columns of theta
@@ -45,15 +45,6 @@ class Aligned:
         self.params = [{"yaw": theta[b, 0:1], "trans": theta[b, 1:4], "scale": theta[b, 4:5], "latent": latents[b]} for b in range(int(theta.shape[0]))]
 
 
-def _clouds_on(clouds, dev):
-    pts = []
-    for c in clouds:
-        t = c.detach() if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32))
-        t = t.reshape(-1, 3).to(torch.float32)
-        pts.append(t if t.is_cuda else _upload(t, dev))
-    return pts
-
-
 @_lib.traced("align_samples_many")
 def align_samples_many(clouds, normals=None, origin=(0.0, 0.0, 0.0), free_rows=4, eta=0.02, s_max=1.0, seed=0, _device=None):
     """Camera-frame, metric interval rows from what one sensor position sees of each shape: complete.view_samples_many without a pose.
@@ -70,12 +61,7 @@ def align_samples_many(clouds, normals=None, origin=(0.0, 0.0, 0.0), free_rows=4
     B, F = len(clouds), int(free_rows)
     if normals is not None and len(normals) != B:
         raise ValueError("align_samples_many: %d clouds, %d normal arrays" % (B, len(normals)))
-    if not 0 <= F <= MAX_FREE:
-        raise ValueError("align_samples_many: free_rows must be 0 .. %d (got %d)" % (MAX_FREE, F))
-    if not (np.isfinite(eta) and np.isfinite(s_max) and s_max >= 0):
-        raise ValueError("align_samples_many: eta must be finite, s_max finite and not negative")
-    if B > 65535:
-        raise ValueError("align_samples_many: at most 65535 shapes per call")
+    _check_view("align_samples_many", B, F, eta, s_max)
     if B == 0:
         return []
     device = _device
@@ -84,31 +70,7 @@ def align_samples_many(clouds, normals=None, origin=(0.0, 0.0, 0.0), free_rows=4
     dev = torch.device("cuda" if device is None else device)
     if dev.type != "cuda":
         raise _lib.SdfrError("align_samples_many runs on the GPU only; there is no CPU fallback")
-    pts = _clouds_on(clouds, dev)
-    sizes = [int(t.shape[0]) for t in pts]
-    nrm = None
-    if normals is not None:
-        nrm = []
-        for c, n in zip(normals, sizes):
-            t = c.detach() if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float64))
-            t = t.reshape(-1, 3).to(torch.float64)
-            if int(t.shape[0]) != n:
-                raise ValueError("align_samples_many: %d normals for %d points" % (int(t.shape[0]), n))
-            nrm.append(t if t.is_cuda else _upload(t, dev))
-        nrm = torch.cat(nrm).contiguous()
-    ptoff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    N, Pn = int(ptoff[-1]), 3 + F
-    points = torch.cat(pts).contiguous()
-    d_ptoff = _upload(torch.from_numpy(ptoff), dev)
-    org = _upload(torch.tensor([float(v) for v in origin], dtype=torch.float32).reshape(3), dev)
-    rows = torch.empty((N * Pn, 5), dtype=torch.float32, device=dev)
-    flags = torch.empty((B,), dtype=torch.int32, device=dev)
-    Pt = _lib.ptr
-    with _lib.guard(dev):
-        _lib.check(_lib.lib().sdfr_align_samples(Pt(points) if N else None, Pt(nrm) if (nrm is not None and N) else None, N, Pt(d_ptoff), B, Pt(org), 0, F,
-                                                 float(eta), float(s_max), int(seed) & 0x7FFFFFFFFFFFFFFF, Pt(rows) if N else None, Pt(flags),
-                                                 _lib.stream_ptr()), "sdfr_align_samples")
-    return [BoundSamples(rows[int(ptoff[b]) * Pn:int(ptoff[b + 1]) * Pn], flags[b]) for b in range(B)]
+    return _view_rows("align_samples_many", "sdfr_align_samples", clouds, normals, origin, F, eta, s_max, seed, dev)
 
 
 def _rates(fit, lr, lr_pose):
@@ -126,6 +88,53 @@ def _rates(fit, lr, lr_pose):
         raise ValueError("align_many: the learning rates must be finite and not negative")
     on = {i for f in fit for i in FIT_KEYS[f]}
     return (float(lr) if "latent" in fit else 0.0), [r if i in on else 0.0 for i, r in enumerate(per)]
+
+
+class _PoseFit(_Fit):
+    """encode._fit's description of the pose-and-shape fit: the sdfr_align_* calls, the camera-frame point beside lo and hi among a row's side
+    arrays, five gradient columns after the latent's, and theta, its Adam state and the pose row as per-shape state beside the latent."""
+    step_call, ws_call, extra = "sdfr_align_step", "sdfr_align_ws_bytes", 5
+
+    def __init__(self, params_list, samples, make_samples, lr, lr_pose, seed):
+        _Fit.__init__(self, "align_many", "sdfr_align_rows", "sdfr_align_reduce", 5, "qx qy qz lo hi", "BoundSamples.load(path, device)",
+                      [] if samples is None else samples, lr, None, seed)
+        self.params_list, self.make_samples, self.lr_pose = params_list, make_samples, lr_pose
+        self.B, self.row_floats = len(params_list), 5                     # cam (3 words), lo, hi
+
+    def check(self, Ld):
+        self.check_rows()
+        for p in self.params_list:
+            if int(np.prod(tuple(p["latent"].shape))) != Ld:
+                raise ValueError("align_many: a start latent of %d elements for a decoder of latent size %d" % (int(np.prod(tuple(p["latent"].shape))), Ld))
+
+    def start(self, dev, Ld):
+        if self.make_samples is not None:
+            self.samples = self.make_samples(dev)
+        if self.B == 0:
+            self.theta = torch.zeros((0, 5), dtype=torch.float32, device=dev)
+            return torch.zeros((0, Ld), dtype=torch.float32, device=dev)
+        from .verify import _pose_rows
+        pose0, z = _pose_rows(self.params_list, dev)
+        yaws = [torch.as_tensor(p["yaw"]).detach().reshape(-1)[:1].to(torch.float32) for p in self.params_list]
+        yaw = torch.stack(yaws) if all(y.is_cuda for y in yaws) else _upload(torch.stack([y.cpu() for y in yaws]), dev)
+        self.theta = theta = torch.cat([yaw.to(dev), pose0[:, 2:]], 1).contiguous()
+        # the pose row as sdfr_align_step writes it: cos and sin in double of the float32 yaw, rounded once
+        self.pose = torch.cat([torch.cos(theta[:, :1].double()).float(), torch.sin(theta[:, :1].double()).float(), theta[:, 1:]], 1).contiguous()
+        self.tm, self.tv = torch.zeros_like(theta), torch.zeros_like(theta)
+        return z.clone().contiguous()
+
+    def alloc(self, n_max, dev):
+        self.cam = torch.empty((n_max, 3), dtype=torch.float32, device=dev)
+        self.lo, self.hi = (torch.empty((n_max,), dtype=torch.float32, device=dev) for _ in range(2))
+
+    def group(self, b0, inputs, J, NI):
+        P = _lib.ptr
+        pose, cam, lo, hi = P(self.pose[b0:]), P(self.cam), P(self.lo), P(self.hi)
+        return ((pose, inputs, cam, lo, hi), (pose, None, None, None, None), (lo, hi, J, NI, cam, pose),
+                (P(self.theta[b0:]), P(self.tm[b0:]), P(self.tv[b0:]), pose))
+
+    def rates(self, f):
+        return self.lr * f, (ctypes.c_float * 5)(*[r * f for r in self.lr_pose])
 
 
 @_lib.traced("align_many")
@@ -149,123 +158,26 @@ def align_many(dsdf, params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0), 
 
     Returns an Aligned.  See the module docstring for what the defaults are."""
     params_list = list(params_list)
-    B = len(params_list)
-    iters, k_req, F = int(iters), int(rows_per_iter), int(free_rows)
+    B, F = len(params_list), int(free_rows)
     lr_lat, lr_p = _rates(fit, lr, lr_pose)
-    if iters < 0 or iters >= MAX_ITERS:
-        raise ValueError("align_many: iters must be 0 .. 2^24 - 1 (got %d)" % iters)
-    if k_req < 1:
-        raise ValueError("align_many: rows_per_iter must be at least 1 (got %d)" % k_req)
-    if not float(clamp) > 0:
-        raise ValueError("align_many: clamp must be positive")
-    if lr_step is not None and int(lr_step) < 1:
-        raise ValueError("align_many: lr_step must be at least 1")
-    if not 0 <= F <= MAX_FREE:
-        raise ValueError("align_many: free_rows must be 0 .. %d (got %d)" % (MAX_FREE, F))
-    if not (np.isfinite(eta) and np.isfinite(s_max) and s_max >= 0):
-        raise ValueError("align_many: eta must be finite, s_max finite and not negative")
+    _check_view("align_many", B, F, eta, s_max)
+    make = None
     if samples is None:
         clouds = list(clouds)
         if len(clouds) != B:
             raise ValueError("align_many: %d parameter sets, %d clouds" % (B, len(clouds)))
         if normals is not None and len(normals) != B:
             raise ValueError("align_many: %d parameter sets, %d normal arrays" % (B, len(normals)))
+
+        def make(dev):
+            nrm = normals
+            if nrm is None:
+                nrm = [_cloud_normals(c) if len(c) else torch.zeros((0, 3), dtype=torch.float64, device=dev) for c in _on_device(clouds, torch.float32, dev)]
+            return align_samples_many(clouds, nrm, origin, F, eta, s_max, seed, _device=dev)
     else:
         samples = [samples] if isinstance(samples, BoundSamples) else list(samples)
         if len(samples) != B:
             raise ValueError("align_many: %d parameter sets, %d sample sets" % (B, len(samples)))
-        for s in samples:
-            if s.rows.dim() != 2 or s.rows.shape[1] != 5:
-                raise ValueError("align_many: sample rows must be [n][5] = qx qy qz lo hi")
-    Ld = int(dsdf.latent_size)
-    if not 1 <= Ld <= 256:
-        raise ValueError("align_many: latent sizes 1 .. 256 (the decoder's is %d)" % Ld)
-    if B > 65535:
-        raise ValueError("align_many: at most 65535 shapes per call")
-    for p in params_list:
-        if int(np.prod(tuple(p["latent"].shape))) != Ld:
-            raise ValueError("align_many: a start latent of %d elements for a decoder of latent size %d" % (int(np.prod(tuple(p["latent"].shape))), Ld))
-    dev = next(dsdf.parameters()).device
-    if dev.type != "cuda":
-        raise _lib.SdfrError("align_many runs on the GPU only (the decoder is on %s); there is no CPU fallback" % dev)
-    if samples is None:
-        if normals is None:
-            normals = [_cloud_normals(c) if len(c) else torch.zeros((0, 3), dtype=torch.float64, device=dev) for c in _clouds_on(clouds, dev)]
-        samples = align_samples_many(clouds, normals, origin, F, eta, s_max, seed, _device=dev)
-    for s in samples:
-        if not s.rows.is_cuda:
-            raise _lib.SdfrError("align_many: the sample rows must be on the GPU (BoundSamples.load(path, device))")
-    counts = [len(s) for s in samples]
-    full = [c for c in counts if c > 0]
-    if draw is None:
-        draw = not (full and min(full) == max(full) and full[0] <= k_req)
-    k = k_req if draw else min([k_req] + full)
-    if k > MAX_ROWS:
-        raise ValueError("align_many: at most 2^20 rows per shape and iteration")
-    lr_step = max(1, iters // 2) if lr_step is None else int(lr_step)
-
-    loss = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
-    flags = torch.zeros((B,), dtype=torch.int32, device=dev)
-    hist = torch.zeros((iters, B), dtype=torch.float32, device=dev) if history else None
-    if B == 0:
-        e = torch.zeros((0, Ld), dtype=torch.float32, device=dev)
-        return Aligned(e, e.clone(), torch.zeros((0, 5), dtype=torch.float32, device=dev), loss, flags, hist, [], bool(unit_latents))
-    from .verify import _pose_rows
-    pose0, z = _pose_rows(params_list, dev)
-    z = z.clone().contiguous()
-    yaws = [torch.as_tensor(p["yaw"]).detach().reshape(-1)[:1].to(torch.float32) for p in params_list]
-    yaw = torch.stack(yaws) if all(y.is_cuda for y in yaws) else _upload(torch.stack([y.cpu() for y in yaws]), dev)
-    theta = torch.cat([yaw.to(dev), pose0[:, 2:]], 1).contiguous()
-    # the pose row as sdfr_align_step writes it: cos and sin in double of the float32 yaw, rounded once
-    pose = torch.cat([torch.cos(theta[:, :1].double()).float(), torch.sin(theta[:, :1].double()).float(), theta[:, 1:]], 1).contiguous()
-    zn = torch.empty_like(z)
-
-    L = _lib.lib()
-    P, ck = _lib.ptr, _lib.check
-    handle, fwd, f16 = _decoder_mode(dsdf, dev)
-    NI = Ld + 3
-    rows = torch.cat([s.rows for s in samples]).float().contiguous() if sum(counts) else torch.zeros((0, 5), dtype=torch.float32, device=dev)
-    S = int(rows.shape[0])
-    off = [0]
-    for c in counts:
-        off.append(off[-1] + c)
-    soff = _upload(torch.tensor(off, dtype=torch.int64), dev)
-    mask_words = 0 if handle.has_ln else int(L.sdfr_decoder_mask_words(handle.h, k))
-    per_shape = k * (4 * (2 * NI + 2 + 5)) + 4 * mask_words
-    nb = max(1, min(B, int(staging_bytes) // max(per_shape, 1)))
-    n_max = nb * k
-    inputs = torch.empty((n_max, NI), dtype=torch.float32, device=dev)
-    J = torch.empty((n_max, NI), dtype=torch.float32, device=dev)
-    cam = torch.empty((n_max, 3), dtype=torch.float32, device=dev)
-    lo, hi, pred, sel = (torch.empty((n_max,), dtype=torch.float32, device=dev) for _ in range(4))
-    idx = torch.arange(n_max, dtype=torch.int32, device=dev)
-    masks = None if handle.has_ln else torch.empty((int(L.sdfr_decoder_mask_words(handle.h, n_max)),), dtype=torch.int32, device=dev)
-    ws_bytes = int(L.sdfr_align_ws_bytes(nb, k, Ld))
-    ws = torch.empty((ws_bytes // 8,), dtype=torch.float64, device=dev)
-    g = torch.empty((nb, Ld + 5), dtype=torch.float64, device=dev)
-    m, v = torch.zeros_like(z), torch.zeros_like(z)
-    tm, tv = torch.zeros_like(theta), torch.zeros_like(theta)
-    cnts = {n: torch.full((1,), n * k, dtype=torch.int32, device=dev) for n in {nb, B % nb or nb}}
-    unit = 1 if unit_latents else 0
-    table_flags = torch.empty((nb,), dtype=torch.int32, device=dev)
-    seed64 = int(seed) & 0x7FFFFFFFFFFFFFFF
-    with _lib.guard(dev):
-        st = _lib.stream_ptr()
-        for b0 in range(0, B, nb):
-            n = min(nb, B - b0)
-            zg, so = z[b0:], soff[b0:]
-            for it in range(iters):
-                f = float(lr_factor) ** (it // lr_step)
-                rates = (ctypes.c_float * 5)(*[r * f for r in lr_p])
-                ck(L.sdfr_align_rows(P(rows), S, P(so), n, b0, k, 1 if draw else 0, seed64, it, P(zg), Ld, unit, P(pose[b0:]), P(inputs), P(cam), P(lo),
-                                     P(hi), P(zn[b0:]), P(flags[b0:]), st), "sdfr_align_rows")
-                decoder_rows(handle, fwd, f16, inputs, n * k, pred, J, sel, masks, idx, cnts[n], st)
-                ck(L.sdfr_align_reduce(P(pred), P(lo), P(hi), P(J), NI, P(cam), P(pose[b0:]), Ld, n, k, float(clamp), P(ws), ws_bytes, P(loss[b0:]),
-                                       P(g), P(flags[b0:]), st), "sdfr_align_reduce")
-                ck(L.sdfr_align_step(P(zg), P(m[b0:]), P(v[b0:]), Ld, n, unit, P(theta[b0:]), P(tm[b0:]), P(tv[b0:]), P(pose[b0:]), P(g), P(loss[b0:]),
-                                     P(flags[b0:]), float(code_reg), lr_lat * f, rates, it + 1, P(hist[:, b0:]) if hist is not None else None, B, st),
-                   "sdfr_align_step")
-            # the latents as the decoder sees the final z (and, with iters = 0, the flags of the table and the pose)
-            ck(L.sdfr_align_rows(None, S, P(so), n, b0, k, 0, seed64, 0, P(zg), Ld, unit, P(pose[b0:]), None, None, None, None, P(zn[b0:]),
-                                 P(flags[b0:] if iters == 0 else table_flags), st), "sdfr_align_rows")
-    return Aligned(zn, z, theta, loss, flags, hist, samples, bool(unit_latents))
+    f = _PoseFit(params_list, samples, make, lr_lat, lr_p, seed)
+    zn, z, loss, flags, hist, unit = _fit(f, dsdf, iters, rows_per_iter, lr_step, lr_factor, clamp, code_reg, unit_latents, seed, history, staging_bytes, draw)
+    return Aligned(zn, z, f.theta, loss, flags, hist, f.samples, unit)

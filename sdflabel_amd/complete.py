@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .encode import _fit, _upload
+from .encode import Encoded, _Fit, _fit, _upload
 from .mesh import STAGING_BYTES
 from .sdf_samples import SdfSamples
 
@@ -91,12 +91,7 @@ def view_samples_many(params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0),
         raise ValueError("view_samples_many: %d parameter sets, %d clouds" % (B, len(clouds)))
     if normals is not None and len(normals) != B:
         raise ValueError("view_samples_many: %d parameter sets, %d normal arrays" % (B, len(normals)))
-    if not 0 <= F <= MAX_FREE:
-        raise ValueError("view_samples_many: free_rows must be 0 .. %d (got %d)" % (MAX_FREE, F))
-    if not (np.isfinite(eta) and np.isfinite(s_max) and s_max >= 0):
-        raise ValueError("view_samples_many: eta must be finite, s_max finite and not negative")
-    if B > 65535:
-        raise ValueError("view_samples_many: at most 65535 shapes per call")
+    _check_view("view_samples_many", B, F, eta, s_max)
     if B == 0:
         return []
     device = _device
@@ -108,35 +103,53 @@ def view_samples_many(params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0),
     if dev.type != "cuda":
         raise _lib.SdfrError("view_samples_many runs on the GPU only; there is no CPU fallback")
     from .verify import _pose_rows
-    pts = []
-    for c in clouds:
-        t = c.detach() if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32))
-        t = t.reshape(-1, 3).to(torch.float32)
-        pts.append(t if t.is_cuda else _upload(t, dev))
+    return _view_rows("view_samples_many", "sdfr_view_samples", clouds, normals, origin, F, eta, s_max, seed, dev, (_pose_rows(params_list, dev)[0],))
+
+
+def _check_view(who, B, F, eta, s_max):
+    if not 0 <= F <= MAX_FREE:
+        raise ValueError("%s: free_rows must be 0 .. %d (got %d)" % (who, MAX_FREE, F))
+    if not (np.isfinite(eta) and np.isfinite(s_max) and s_max >= 0):
+        raise ValueError("%s: eta must be finite, s_max finite and not negative" % who)
+    if B > 65535:
+        raise ValueError("%s: at most 65535 shapes per call" % who)
+
+
+def _on_device(arrays, dtype, dev):
+    """each of `arrays` (tensors or numpy) as a [n][3] tensor of `dtype` on the device, uploaded without waiting"""
+    out = []
+    for c in arrays:
+        t = c.detach() if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32 if dtype == torch.float32 else np.float64))
+        t = t.reshape(-1, 3).to(dtype)
+        out.append(t if t.is_cuda else _upload(t, dev))
+    return out
+
+
+def _view_rows(who, call, clouds, normals, origin, F, eta, s_max, seed, dev, pose=()):
+    """The sample rows of view_samples_many and align.align_samples_many: clouds and normals onto the device, the offset table, the C entry
+    point `call` (`pose`: its pose rows, or none) and the BoundSamples, views of one array."""
+    B = len(clouds)
+    pts = _on_device(clouds, torch.float32, dev)
     sizes = [int(t.shape[0]) for t in pts]
     nrm = None
     if normals is not None:
-        nrm = []
-        for c, n in zip(normals, sizes):
-            t = c.detach() if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float64))
-            t = t.reshape(-1, 3).to(torch.float64)
+        nrm = _on_device(normals, torch.float64, dev)
+        for t, n in zip(nrm, sizes):
             if int(t.shape[0]) != n:
-                raise ValueError("view_samples_many: %d normals for %d points" % (int(t.shape[0]), n))
-            nrm.append(t if t.is_cuda else _upload(t, dev))
+                raise ValueError("%s: %d normals for %d points" % (who, int(t.shape[0]), n))
         nrm = torch.cat(nrm).contiguous()
     ptoff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     N, Pn = int(ptoff[-1]), 3 + F
     points = torch.cat(pts).contiguous()
     d_ptoff = _upload(torch.from_numpy(ptoff), dev)
-    pose, _ = _pose_rows(params_list, dev)
     org = _upload(torch.tensor([float(v) for v in origin], dtype=torch.float32).reshape(3), dev)
     rows = torch.empty((N * Pn, 5), dtype=torch.float32, device=dev)
     flags = torch.empty((B,), dtype=torch.int32, device=dev)
     Pt = _lib.ptr
     with _lib.guard(dev):
-        _lib.check(_lib.lib().sdfr_view_samples(Pt(points) if N else None, Pt(nrm) if (nrm is not None and N) else None, N, Pt(d_ptoff), B, Pt(pose),
-                                                Pt(org), 0, F, float(eta), float(s_max), int(seed) & 0x7FFFFFFFFFFFFFFF, Pt(rows) if N else None,
-                                                Pt(flags), _lib.stream_ptr()), "sdfr_view_samples")
+        _lib.check(getattr(_lib.lib(), call)(Pt(points) if N else None, Pt(nrm) if (nrm is not None and N) else None, N, Pt(d_ptoff), B,
+                                             *[Pt(p) for p in pose], Pt(org), 0, F, float(eta), float(s_max), int(seed) & 0x7FFFFFFFFFFFFFFF,
+                                             Pt(rows) if N else None, Pt(flags), _lib.stream_ptr()), call)
     return [BoundSamples(rows[int(ptoff[b]) * Pn:int(ptoff[b + 1]) * Pn], flags[b]) for b in range(B)]
 
 
@@ -148,8 +161,8 @@ def fit_many(dsdf, samples, iters=800, rows_per_iter=8000, lr=5e-3, lr_step=None
     the clamped prediction to the clamped interval, `.flags` bit 1 (2) means no row with a finite prediction and usable bounds.  On
     BoundSamples.from_sdf(s) the results are encode_many's on s in every bit."""
     samples = [samples] if isinstance(samples, BoundSamples) else list(samples)
-    return _fit("fit_many", "sdfr_bound_rows", "sdfr_bound_reduce", 5, "x y z lo hi", dsdf, samples, iters, rows_per_iter, lr, lr_step, lr_factor, clamp,
-                code_reg, unit_latents, init, seed, history, staging_bytes, draw)
+    fit = _Fit("fit_many", "sdfr_bound_rows", "sdfr_bound_reduce", 5, "x y z lo hi", "BoundSamples.load(path, device)", samples, lr, init, seed)
+    return Encoded(*_fit(fit, dsdf, iters, rows_per_iter, lr_step, lr_factor, clamp, code_reg, unit_latents, seed, history, staging_bytes, draw))
 
 
 def _cloud_normals(cloud, radius=1.0, max_nn=30):

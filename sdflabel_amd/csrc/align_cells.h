@@ -1,6 +1,7 @@
 // Per-element rules of the pose-and-shape fit to one view (align.hip): the camera-frame observation rows one point gives, what a drawn row
 // becomes under the iteration's pose, what a row adds to its shape's loss and to the gradient with respect to the latent AND the pose
-// (yaw, trans, scale), and the update of the pose.  Plain functions, compiled for the device by align.hip and for the host by
+// (yaw, trans, scale), and the update of the pose -- and the policy structs (AlnPosedRows, AlnRowRule, AlnCols, AlnPoseStep) through which
+// the kernels of encode_kernels.h see them.  Plain functions and structs, compiled for the device by align.hip and for the host by
 // tests/align_host/align_host.cpp, which is compared with the numpy restatement (tests/_align_ref.py) bit for bit.  Every operation rounds
 // on its own (-ffp-contract=off).  DESIGN.md 7m has the rules.
 #pragma once
@@ -14,57 +15,16 @@
 #define ALN_BAD_POSE 16          // flags, bit 4: pose[b] fails cpl_pose_ok; every row of the shape is invalid.  (complete_cells.h's
                                  // CPL_BAD_POSE is 4, which in an iteration's flag word is ENC_SKIPPED; the fit keeps the two apart.)
 
-// one observation slot: the float64 position rounded once; valid only if the caller says so and the float32 position is finite.  There is
-// no cube in the camera frame.
-ENC_HD void aln_store(float* row, bool valid, const double* q, float lo, float hi) {
-    const float f0 = (float)q[0], f1 = (float)q[1], f2 = (float)q[2];
-    const bool in = valid && isfinite(f0) && isfinite(f1) && isfinite(f2);
-    const float nan = nanf("");
-    row[0] = in ? f0 : 0.f;
-    row[1] = in ? f1 : 0.f;
-    row[2] = in ? f2 : 0.f;
-    row[3] = in ? lo : nan;
-    row[4] = in ? hi : nan;
-}
-
-// The P = 3 + F rows of one observed point p (camera frame, metres), written to out[P][5].  n: the camera-frame normal (float64 [3]) or
-// NULL; origin: the sensor (camera frame); usable: the point has an owner -- otherwise every slot is invalid and nothing of p or n is used.
-// In float64, in this order:  len = sqrt((n0 n0 + n1 n1) + n2 n2), n^ = n / len;  slot 1, 2 = p +- eta n^;  d = p - o,
-// r = sqrt((d0 d0 + d1 d1) + d2 d2), d^ = d / r, reach = fmin(s_max, r), s = ((f + u) / F) reach, slot 3 + f = p - s d^ with [0, float32(s)].
+// The P = 3 + F rows of one observed point p (camera frame, metres), written to out[P][5]: cpl_point_rows of p, the sensor `origin` and the
+// normal n (float64 [3], or NULL) as they are, and the finite rule -- there is no cube in the camera frame.  usable: the point has an
+// owner; a point that is not finite gives invalid slots too.
 ENC_HD void aln_sample_row(const float* p, const double* n, const float* origin, bool usable, uint64_t seed, int shape, int64_t i, int F, double eta,
                            double s_max, float* out) {
-    const double zero3[3] = {0.0, 0.0, 0.0};
     const bool p_ok = usable && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
-    if (!p_ok) {
-        for (int j = 0; j < 3 + F; ++j) aln_store(out + ALN_ROW * j, false, zero3, 0.f, 0.f);
-        return;
-    }
-    const double x[3] = {(double)p[0], (double)p[1], (double)p[2]};
-    aln_store(out, true, x, 0.f, 0.f);
-    bool n_ok = false;
-    double nh[3] = {0.0, 0.0, 0.0};
-    if (n) {
-        const double len = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
-        n_ok = verify_finite(len) && len > 0.0;
-        if (n_ok) nh[0] = n[0] / len, nh[1] = n[1] / len, nh[2] = n[2] / len;
-    }
-    const float fe = (float)eta;
-    double y[3];
-    for (int a = 0; a < 3; ++a) y[a] = x[a] + eta * nh[a];
-    aln_store(out + ALN_ROW, n_ok, y, fe, fe);
-    for (int a = 0; a < 3; ++a) y[a] = x[a] - eta * nh[a];
-    aln_store(out + 2 * ALN_ROW, n_ok, y, -fe, -fe);
-    const double dx = x[0] - (double)origin[0], dy = x[1] - (double)origin[1], dz = x[2] - (double)origin[2];
-    const double r = sqrt((dx * dx + dy * dy) + dz * dz);
-    const bool r_ok = verify_finite(r) && r > 0.0;
-    const double d0 = r_ok ? dx / r : 0.0, d1 = r_ok ? dy / r : 0.0, d2 = r_ok ? dz / r : 0.0;
-    const double reach = fmin(s_max, r);
-    for (int f = 0; f < F; ++f) {
-        const double u = cpl_u(seed, shape, i, f);
-        const double s = (((double)f + u) / (double)F) * reach;
-        y[0] = x[0] - s * d0, y[1] = x[1] - s * d1, y[2] = x[2] - s * d2;
-        aln_store(out + ALN_ROW * (3 + f), r_ok, y, 0.f, (float)s);
-    }
+    double x[3] = {0.0, 0.0, 0.0}, o[3] = {0.0, 0.0, 0.0};
+    if (p_ok)
+        for (int a = 0; a < 3; ++a) x[a] = (double)p[a], o[a] = (double)origin[a];
+    cpl_point_rows(p_ok, x, o, p_ok ? n : nullptr, false, seed, shape, i, F, eta, s_max, out);
 }
 
 // The drawn observation (q, lo, hi) under the iteration's pose: x = float32(verify_point_x64(q, pose)).  A row whose x leaves [-1, 1]^3,
@@ -82,6 +42,41 @@ ENC_HD void aln_row(const float* q, const float* pose, bool pose_ok, float* x, f
 ENC_HD int32_t aln_rows_flags(bool bad, int64_t count, bool pose_ok) {
     return bad ? ENC_BAD_TABLE : (count == 0 ? ENC_EMPTY : (pose_ok ? 0 : ALN_BAD_POSE));
 }
+
+// The rows kernel's policy (encode_cells.h) for observation rows under pose[b]: the side arrays are the camera-frame point, lo and hi
+// (aln_row), and the workgroup keeps the lattice position itself until the decoder's inputs are written.
+struct AlnPosedRows {
+    static constexpr int W = ALN_ROW;
+    struct Shape {
+        float ps[VERIFY_POSE];
+        bool ok;
+    };
+    struct Staged {
+        float x[3];
+    };
+    const float* pose;
+    float *cam, *lo, *hi;
+    ENC_HDM Shape shape(int b) const {
+        Shape s;
+        for (int a = 0; a < VERIFY_POSE; ++a) s.ps[a] = pose[VERIFY_POSE * b + a];
+        s.ok = cpl_pose_ok(s.ps);
+        return s;
+    }
+    ENC_HDM int32_t flags(const Shape& s, bool bad, int64_t count) const { return aln_rows_flags(bad, count, s.ok); }
+    ENC_HDM Staged stage(const Shape& s, const float* samples, int64_t src, int64_t i) const {
+        float q[3] = {0.f, 0.f, 0.f}, l = 0.f, h = 0.f;
+        Staged st = {{0.f, 0.f, 0.f}};
+        if (src >= 0) {
+            const float* row = samples + src * W;
+            q[0] = row[0], q[1] = row[1], q[2] = row[2], l = row[3], h = row[4];
+            aln_row(q, s.ps, s.ok, st.x, &l, &h);
+        }
+        cam[3 * i] = q[0], cam[3 * i + 1] = q[1], cam[3 * i + 2] = q[2];
+        lo[i] = l, hi[i] = h;
+        return st;
+    }
+    ENC_HDM float xyz(const float*, const Staged& st, int a) const { return st.x[a]; }
+};
 
 // the metric prediction the row rule sees: scale p, one float32 rounding
 ENC_HD float aln_metric(float p, const float* pose) { return pose[5] * p; }
@@ -134,6 +129,27 @@ ENC_HD double aln_value(int c, int L, float w, double e, int ok, float p, const 
     return c == G ? e : (ok ? 1.0 : 0.0);
 }
 
+// the reduce's row rule (encode_cells.h): the interval rule on the metric prediction
+struct AlnRowRule {
+    const float *lo, *hi, *pose;
+    ENC_HDM EncRow operator()(float p, int64_t i, int b, float clamp) const { return cpl_row(aln_metric(p, pose + VERIFY_POSE * b), lo[i], hi[i], clamp); }
+};
+
+// The reduce's column rule: the L + 5 gradient columns.  The five pose columns of a row (float64 divisions and a rotation each) are formed
+// once per row into the EXTRA words; the latent columns, one product each, where they are summed.
+struct AlnCols {
+    static constexpr int EXTRA = ALN_POSE;
+    const float *pred, *J, *cam, *pose;
+    int Jstride, L;
+    ENC_HDM void prepare(double* x, float w, int64_t i, int b) const {
+        for (int c = 0; c < ALN_POSE; ++c) x[c] = aln_value(L + c, L, w, 0.0, 0, pred[i], J + i * Jstride, cam + 3 * i, pose + VERIFY_POSE * b);
+    }
+    ENC_HDM double operator()(int c, int, float w, double e, int ok, int64_t i, int b, const double* x) const {
+        if (c >= L && c < L + ALN_POSE) return x[c - L];
+        return aln_value(c, L, w, e, ok, pred[i], J + i * Jstride, cam + 3 * i, pose + VERIFY_POSE * b);
+    }
+};
+
 // the pose row of theta = yaw, tx, ty, tz, scale: cos and sin in double of the float32 yaw, rounded once
 ENC_HD void aln_pose_row(const float* theta, float* pose) {
     pose[0] = (float)cos((double)theta[0]);
@@ -158,9 +174,29 @@ ENC_HD float aln_scale_after(const float* theta, const float* tm, const float* t
     return s;
 }
 
-// latent_adam on every pose parameter whose rate is not 0 (a rate of 0 leaves the parameter and its state untouched), then the next pose row
-ENC_HD void aln_pose_step(float* theta, float* tm, float* tv, const double* g, int L, const float* lr, float bc1, float bc2, float* pose) {
+// latent_adam on every pose parameter whose rate is not 0 (a rate of 0 leaves the parameter and its state untouched), then the next pose row.
+// The arrays do not overlap, and the signature says so: the device then loads the fifteen words of state at once, not parameter by parameter.
+ENC_HD void aln_pose_step(float* __restrict__ theta, float* __restrict__ tm, float* __restrict__ tv, const double* __restrict__ g, int L,
+                          const float* __restrict__ lr, float bc1, float bc2, float* __restrict__ pose) {
     for (int i = 0; i < ALN_POSE; ++i)
         if (lr[i] != 0.f) latent_adam(&theta[i], &tm[i], &tv[i], (float)g[L + i], lr[i], bc1, bc2);
     aln_pose_row(theta, pose);
 }
+
+// The step kernel's pose policy (encode_cells.h): five pose parameters after the latent.  A shape with an unusable pose, a pose gradient
+// that is not finite or a scale the update would not leave positive is not stepped; a latent rate of 0 leaves z, m and v alone, as a pose
+// rate of 0 does its parameter.
+struct AlnPoseStep {
+    static constexpr int EXTRA = ALN_POSE;
+    static constexpr int SKIP = ENC_EMPTY | ENC_NO_ROWS | ENC_BAD_TABLE | ALN_BAD_POSE;
+    float *theta, *tm, *tv, *pose;
+    float lr[ALN_POSE];
+    ENC_HDM bool ok(int b, const double* g, int L, float bc1, float bc2) const {
+        const float sc = aln_scale_after(theta + ALN_POSE * b, tm + ALN_POSE * b, tv + ALN_POSE * b, g, L, lr[4], bc1, bc2);
+        return aln_pose_grad_ok(g, L) && isfinite(sc) && sc > 0.f;
+    }
+    ENC_HDM bool steps_latent(float lr_latent) const { return lr_latent != 0.f; }
+    ENC_HDM void step(int b, const double* g, int L, float bc1, float bc2) const {
+        aln_pose_step(theta + ALN_POSE * b, tm + ALN_POSE * b, tv + ALN_POSE * b, g, L, lr, bc1, bc2, pose + VERIFY_POSE * b);
+    }
+};

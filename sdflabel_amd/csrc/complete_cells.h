@@ -1,8 +1,9 @@
 // Per-element rules of shape completion from one view (complete.hip): what a row with an interval target [lo, hi] contributes to its shape's
 // loss and latent gradient, and the rows one observed point gives -- the point, two points offset along its normal, and free-space points
-// on its sensor ray.  Plain functions, compiled for the device by complete.hip and for the host by tests/complete_host/complete_host.cpp,
-// which is compared with the numpy restatement (tests/_complete_ref.py) bit for bit.  Every operation rounds on its own (-ffp-contract=off).
-// DESIGN.md 7l has the rules.
+// on its sensor ray (cpl_point_rows: THE per-point function, which align_cells.h's camera-frame rows go through too) --, and the row policy
+// and row rule the kernels of encode_kernels.h take for such rows.  Plain functions and structs, compiled for the device by complete.hip
+// and for the host by tests/complete_host/complete_host.cpp, which is compared with the numpy restatement (tests/_complete_ref.py) bit for
+// bit.  Every operation rounds on its own (-ffp-contract=off).  DESIGN.md 7l has the rules.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -67,10 +68,12 @@ ENC_HD double cpl_u(uint64_t seed, int shape, int64_t i, int f) {
     return (double)(h >> 11) * 1.1102230246251565e-16;          // 2^-53
 }
 
-// one slot: the float64 position rounded once; valid only if the caller says so and the float32 position is finite and in [-1, 1]^3
-ENC_HD void cpl_store(float* row, bool valid, const double* x, float lo, float hi) {
+// one slot: the float64 position rounded once; valid only if the caller says so and the float32 position passes the store rule -- in
+// [-1, 1]^3 with `cube` (the lattice frame), finite without (the camera frame has no cube)
+ENC_HD void cpl_store(float* row, bool valid, bool cube, const double* x, float lo, float hi) {
     const float f0 = (float)x[0], f1 = (float)x[1], f2 = (float)x[2];
-    const bool in = valid && fabsf(f0) <= 1.0f && fabsf(f1) <= 1.0f && fabsf(f2) <= 1.0f;            // (a NaN or an infinity is not)
+    const bool in = valid && (cube ? fabsf(f0) <= 1.0f && fabsf(f1) <= 1.0f && fabsf(f2) <= 1.0f            // (a NaN or an infinity is not)
+                                   : isfinite(f0) && isfinite(f1) && isfinite(f2));
     const float nan = nanf("");
     row[0] = in ? f0 : 0.f;
     row[1] = in ? f1 : 0.f;
@@ -79,37 +82,32 @@ ENC_HD void cpl_store(float* row, bool valid, const double* x, float lo, float h
     row[4] = in ? hi : nan;
 }
 
-// The P = 3 + F rows of one observed point p (camera frame) of a shape with pose row `pose`, written to out[P][5].  n: the camera-frame
-// normal (float64 [3]) or NULL; origin: the sensor's position (camera frame); usable: the shape's pose is (cpl_pose_ok) and the point
-// has an owner -- otherwise every slot is invalid and nothing of p, n or pose is used.
-ENC_HD void cpl_view_row(const float* p, const double* n, const float* pose, const float* origin, bool usable, uint64_t seed, int shape, int64_t i,
-                         int F, double eta, double s_max, float* out) {
-    const double zero3[3] = {0.0, 0.0, 0.0};
+// THE P = 3 + F rows of one observed point, written to out[P][5]: the point at x and the sensor at o, both in the frame the rows are in
+// (float64 [3]); m: the normal in that frame, of any length (float64 [3]), or NULL.  usable = false: every slot is invalid and nothing of
+// x, o or m is used.  In float64, in this order:  len = sqrt((m0 m0 + m1 m1) + m2 m2), n^ = m / len;  slot 1, 2 = x +- eta n^ with
+// [+-eta, +-eta];  d = x - o, r = sqrt((d0 d0 + d1 d1) + d2 d2), d^ = d / r, reach = fmin(s_max, r), s = ((f + u) / F) reach,
+// slot 3 + f = x - s d^ with [0, float32(s)].
+ENC_HD void cpl_point_rows(bool usable, const double* x, const double* o, const double* m, bool cube, uint64_t seed, int shape, int64_t i, int F,
+                           double eta, double s_max, float* out) {
     if (!usable) {
-        for (int j = 0; j < 3 + F; ++j) cpl_store(out + CPL_ROW * j, false, zero3, 0.f, 0.f);
+        const double zero3[3] = {0.0, 0.0, 0.0};
+        for (int j = 0; j < 3 + F; ++j) cpl_store(out + CPL_ROW * j, false, cube, zero3, 0.f, 0.f);
         return;
     }
-    double x[3], o[3];
-    verify_point_x64(p, pose, x);
-    verify_point_x64(origin, pose, o);
-    cpl_store(out, true, x, 0.f, 0.f);
-    // the normal: diag(1, -1, 1) rot_yaw^T n, then divided by its length
+    cpl_store(out, true, cube, x, 0.f, 0.f);
     bool n_ok = false;
     double nh[3] = {0.0, 0.0, 0.0};
-    if (n) {
-        const double c = (double)pose[0], s = (double)pose[1];
-        const double a0 = c * n[0], a1 = s * n[2], b0 = s * n[0], b1 = c * n[2];
-        const double m0 = a0 - a1, m1 = -n[1], m2 = b0 + b1;
-        const double len = sqrt((m0 * m0 + m1 * m1) + m2 * m2);
+    if (m) {
+        const double len = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
         n_ok = verify_finite(len) && len > 0.0;
-        if (n_ok) nh[0] = m0 / len, nh[1] = m1 / len, nh[2] = m2 / len;
+        if (n_ok) nh[0] = m[0] / len, nh[1] = m[1] / len, nh[2] = m[2] / len;
     }
     const float fe = (float)eta;
     double y[3];
     for (int a = 0; a < 3; ++a) y[a] = x[a] + eta * nh[a];
-    cpl_store(out + CPL_ROW, n_ok, y, fe, fe);
+    cpl_store(out + CPL_ROW, n_ok, cube, y, fe, fe);
     for (int a = 0; a < 3; ++a) y[a] = x[a] - eta * nh[a];
-    cpl_store(out + 2 * CPL_ROW, n_ok, y, -fe, -fe);
+    cpl_store(out + 2 * CPL_ROW, n_ok, cube, y, -fe, -fe);
     // the ray from the sensor to the point
     const double dx = x[0] - o[0], dy = x[1] - o[1], dz = x[2] - o[2];
     const double r = sqrt((dx * dx + dy * dy) + dz * dz);
@@ -120,6 +118,33 @@ ENC_HD void cpl_view_row(const float* p, const double* n, const float* pose, con
         const double u = cpl_u(seed, shape, i, f);
         const double s = (((double)f + u) / (double)F) * reach;
         y[0] = x[0] - s * d0, y[1] = x[1] - s * d1, y[2] = x[2] - s * d2;
-        cpl_store(out + CPL_ROW * (3 + f), r_ok, y, 0.f, (float)s);
+        cpl_store(out + CPL_ROW * (3 + f), r_ok, cube, y, 0.f, (float)s);
     }
 }
+
+// The rows of one observed point p (camera frame) of a shape with pose row `pose`, in the lattice frame: cpl_point_rows of
+// verify_point_x64 of p and of the sensor `origin`, the normal n (camera frame, float64 [3], or NULL) taken through
+// diag(1, -1, 1) rot_yaw^T, and the cube rule.  usable: the shape's pose is (cpl_pose_ok) and the point has an owner -- otherwise nothing
+// of p, n or pose is used.
+ENC_HD void cpl_view_row(const float* p, const double* n, const float* pose, const float* origin, bool usable, uint64_t seed, int shape, int64_t i,
+                         int F, double eta, double s_max, float* out) {
+    double x[3] = {0.0, 0.0, 0.0}, o[3] = {0.0, 0.0, 0.0}, m[3] = {0.0, 0.0, 0.0};
+    if (usable) {
+        verify_point_x64(p, pose, x);
+        verify_point_x64(origin, pose, o);
+        if (n) {
+            const double c = (double)pose[0], s = (double)pose[1];
+            const double a0 = c * n[0], a1 = s * n[2], b0 = s * n[0], b1 = c * n[2];
+            m[0] = a0 - a1, m[1] = -n[1], m[2] = b0 + b1;
+        }
+    }
+    cpl_point_rows(usable, x, o, (usable && n) ? m : nullptr, true, seed, shape, i, F, eta, s_max, out);
+}
+
+// the two fits to interval rows share the rows kernel's policy for samples of x y z lo hi, and the row rule
+typedef EncTargetRows<CPL_ROW> CplBoundRows;
+
+struct CplBoundRule {
+    const float *lo, *hi;
+    ENC_HDM EncRow operator()(float p, int64_t i, int, float clamp) const { return cpl_row(p, lo[i], hi[i], clamp); }
+};

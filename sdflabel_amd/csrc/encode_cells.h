@@ -1,7 +1,8 @@
 // Per-element rules of the shape encoder (encode.hip): which sample a row takes, what a row contributes to its shape's loss and latent
-// gradient, the order in which a chunk of rows is summed, and the gradient an Adam update of a latent element sees.  Plain functions,
-// compiled for the device by encode.hip and for the host by tests/encode_host/encode_host.cpp, which loops over every thread's work and is
-// compared with the numpy restatement (tests/_encode_ref.py) bit for bit.  DESIGN.md 7k has the rules.
+// gradient, the order in which a chunk of rows is summed, and the gradient an Adam update of a latent element sees -- and, at the end, the
+// policy structs through which the kernels of encode_kernels.h see them.  Plain functions and structs, compiled for the device by
+// encode.hip and for the host by tests/encode_host/encode_host.cpp, which loops over every thread's work (tests/fit_host.h) and is compared
+// with the numpy restatement (tests/_encode_ref.py) bit for bit.  DESIGN.md 7k has the rules.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -10,7 +11,13 @@
 #include "train_cells.h"
 
 #define ENC_HD TRAIN_HD
+#if defined(__HIPCC__)
+#define ENC_HDM __host__ __device__ __forceinline__          // a member function of a policy struct
+#else
+#define ENC_HDM
+#endif
 
+#define ENC_THREADS 256          // threads of a workgroup of the rows, chunk, step and samples kernels
 #define ENC_CHUNK 1024           // rows per partial sum: a constant, so the summation order is a function of k alone
 #define ENC_SLOTS 64             // accumulators of a chunk: slot j sums the chunk's rows j, j + 64, ... in ascending order
 #define ENC_COLS 32              // columns a workgroup folds at a time (LDS: ENC_SLOTS x ENC_COLS doubles)
@@ -106,3 +113,57 @@ ENC_HD void enc_bias(int t, float* bc1, float* bc2) {
     *bc1 = (float)(1.0 - pow(0.9, (double)t));
     *bc2 = (float)(1.0 - pow(0.999, (double)t));
 }
+
+// ---- the policies of the fits' kernels --------------------------------------------------------------------------------------------------------
+// Plain structs of pointers and rules, instantiated by the kernels of encode_kernels.h and by a host program alike.
+//
+// A ROW POLICY of the rows kernel: W floats a sample; shape(b) what a workgroup keeps of its shape; flags() the shape's flag word; stage()
+// stores the side arrays of row i (an index into the [B k] arrays) from sample `src` (a row of `samples`; -1: a zero row) and returns what
+// the workgroup keeps of the row until the decoder's inputs are written; xyz() gives word a of the row's position from that.
+// EncTargetRows: x y z and W - 3 target words, word 3 to t0, word 4 (W = 5) to t1; the position is read where it is written.
+template <int WIDTH>
+struct EncTargetRows {
+    static constexpr int W = WIDTH;
+    struct Shape {};
+    typedef int64_t Staged;
+    float *t0, *t1;
+    ENC_HDM Shape shape(int) const { return Shape(); }
+    ENC_HDM int32_t flags(const Shape&, bool bad, int64_t count) const { return bad ? ENC_BAD_TABLE : (count == 0 ? ENC_EMPTY : 0); }
+    ENC_HDM Staged stage(const Shape&, const float* samples, int64_t src, int64_t i) const {
+        t0[i] = src < 0 ? 0.f : samples[src * W + 3];
+        if (W == 5) t1[i] = src < 0 ? 0.f : samples[src * W + 4];
+        return src;
+    }
+    ENC_HDM float xyz(const float* samples, const Staged& src, int a) const { return samples[src * W + a]; }
+};
+typedef EncTargetRows<4> EncExactRows;
+
+// A ROW RULE of the reduce gives the EncRow of row i of shape b from its prediction; a COLUMN RULE the value of column c < G + 2 of that row
+// (G gradient columns, then the loss and the count of ok rows).  A column rule may keep EXTRA float64 words a row, written once per row
+// (prepare) before the columns are summed: values that are costly and shared by no other row.  What is summed, and in which order, does not
+// depend on where a value was formed.
+struct EncExactRule {
+    const float* target;
+    ENC_HDM EncRow operator()(float p, int64_t i, int, float clamp) const { return enc_row(p, target[i], clamp); }
+};
+
+struct EncLatentCols {               // the latent fits: the latent columns of J, G = L
+    static constexpr int EXTRA = 0;
+    const float* J;
+    int Jstride;
+    ENC_HDM void prepare(double*, float, int64_t, int) const {}
+    ENC_HDM double operator()(int c, int G, float w, double e, int ok, int64_t i, int, const double*) const {
+        return enc_value(c, G, w, e, ok, J + i * Jstride);
+    }
+};
+
+// A POSE POLICY of the step kernel: EXTRA gradient columns after the latent's, the flags that keep a shape from being stepped, ok() whatever
+// else does, whether the latent is stepped at the rate lr, and the step of the pose itself (thread 0).  EncNoPose: a latent alone, which
+// Adam visits at lr == 0 too (m and v move).
+struct EncNoPose {
+    static constexpr int EXTRA = 0;
+    static constexpr int SKIP = ENC_EMPTY | ENC_NO_ROWS | ENC_BAD_TABLE;
+    ENC_HDM bool ok(int, const double*, int, float, float) const { return true; }
+    ENC_HDM bool steps_latent(float) const { return true; }
+    ENC_HDM void step(int, const double*, int, float, float) const {}
+};

@@ -87,14 +87,15 @@ def reduce_case(B, k, L, Jstride):
     return _ro(pred, target, J, flags)
 
 
-# (B, L, unit, t)
+# (B, L, unit, t), or (B, L, unit, t, lr) for a learning rate that is not the schedule's
 def step_cases():
-    return [(1, 3, 1, 1), (3, 3, 1, 7), (3, 3, 0, 1), (5, 8, 1, 400), (5, 8, 0, 3), (5, 256, 1, 2), (3, 256, 0, 800)]
+    return [(1, 3, 1, 1), (3, 3, 1, 7), (3, 3, 1, 7, 0.0), (3, 3, 0, 1), (5, 8, 1, 400), (5, 8, 0, 3), (5, 256, 1, 2), (3, 256, 0, 800)]
 
 
 @functools.lru_cache(maxsize=None)
-def step_case(B, L, unit, t):
-    """(z, m, v [B][L], g_zn float64 [B][L], flags [B], code_reg, lr).  Shape 1: z = 0 (with unit the gradient through the 1e-12 floor; without,
+def step_case(B, L, unit, t, lr=None):
+    """(z, m, v [B][L], g_zn float64 [B][L], flags [B], code_reg, lr); lr: the schedule's at step t, or the one given -- sdfr_encode_step at
+    lr = 0 still runs Adam, so m and v move and z does not.  Shape 1: z = 0 (with unit the gradient through the 1e-12 floor; without,
     no regulariser term).  Shape 2: flagged empty.  Shape 3: a NaN gradient element.  Shape 4: a gradient that overflows float32."""
     rng = np.random.default_rng(3000 + 31 * t + 7 * B + L + unit)
     z = (0.3 * rng.standard_normal((B, L))).astype(np.float32)
@@ -110,4 +111,4 @@ def step_case(B, L, unit, t):
         g[3, L // 2] = np.nan
     if B > 4:
         g[4, 0] = 1e60
-    return _ro(z, m, v, g, flags) + (1e-4, 5e-3 * 0.1 ** (t // 400))
+    return _ro(z, m, v, g, flags) + (1e-4, 5e-3 * 0.1 ** (t // 400) if lr is None else lr)

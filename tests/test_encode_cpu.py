@@ -166,13 +166,18 @@ def _host_checks(exe, tmp):
         if B >= 3:
             assert not np.isfinite(want[1][B - 1, 0])
     for case in EC.step_cases():
-        B, L, unit, t = case
+        B, L, unit, t = case[:4]
         z, m, v, g, flags, code_reg, lr = EC.step_case(*case)
         got = host_step(exe, tmp, z, m, v, g, flags, unit, code_reg, lr, t)
         want = ER.step(z, m, v, g, flags, unit, code_reg, lr, t)
         for a, w, n in zip(got, want, ("z", "m", "v", "flags")):
             same_bits(a, w, (case, n))
-        assert not want[3][0] and (want[0][0] != z[0]).all()                       # shape 0 stepped, every element
+        assert not want[3][0]                                                      # shape 0 stepped, every element
+        if lr:
+            assert (want[0][0] != z[0]).all()
+        else:                                                                      # at lr = 0 Adam still runs: z stays, m and v move
+            same_bits(want[0][0], z[0])
+            assert (want[1][0] != m[0]).all() and (want[2][0] != v[0]).all()
         for b in range(2, B):                                                      # flagged, NaN and overflowing gradients: untouched
             assert want[3][b] & ER.SKIPPED
             same_bits(want[0][b], z[b]); same_bits(want[1][b], m[b]); same_bits(want[2][b], v[b])

@@ -139,9 +139,9 @@ def test_reduce_kernel_equals_the_restatement(case):
         same_bits(g, w, (case, n))
 
 
-@pytest.mark.parametrize("case", EC.step_cases(), ids=lambda c: "B%d_L%d_u%d_t%d" % c)
+@pytest.mark.parametrize("case", EC.step_cases(), ids=lambda c: "B%d_L%d_u%d_t%d" % c[:4] + ("_lr0" if len(c) > 4 else ""))
 def test_step_kernel_equals_the_restatement(case):
-    B, L, unit, t = case
+    B, L, unit, t = case[:4]
     z, m, v, g, flags, code_reg, lr = EC.step_case(*case)
     loss = np.linspace(0.01, 0.09, B)
     got = dev_step(z, m, v, g, flags, unit, code_reg, lr, t, loss=loss, history_rows=t if t < 10 else 0)
