@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 420        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 421        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -49,7 +49,8 @@ extern "C" {
  * grid forward's launch order from the last pass, sdfr_mlp_balance_* and sdfr_mlp_forward_balanced, and the per-workgroup tile trace of trace
  * builds, sdfr_debug_set_tile_trace; 417: training the decoder, sdfr_decoder_train_*; 418: encoding shapes under a
  * frozen decoder, sdfr_encode_*; 419: shape completion from one view, sdfr_view_samples and
- * sdfr_bound_*; 420: pose and shape fitted to one view, sdfr_align_*).  A caller built
+ * sdfr_bound_*; 420: pose and shape fitted to one view, sdfr_align_*;
+ * 421: lidar clusters and rough boxes, sdfr_cluster_* and sdfr_lidar_clusters).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -1295,6 +1296,41 @@ int sdfr_align_reduce(const float* pred, const float* lo, const float* hi, const
 int sdfr_align_step(float* z, float* m, float* v, int L, int B, int unit, float* theta, float* tm, float* tv, float* pose, const double* g,
                     const double* loss, int32_t* flags, float code_reg, float lr, const float* lr_pose, int t, float* history, int64_t history_stride,
                     void* stream);
+
+/* ---- lidar clusters and rough boxes (csrc/cluster.hip, SDFR_VERSION 421) ----
+ * Object proposals from a raw scan: Euclidean clusters of the (road-free) cloud and a minimum-area rectangle per cluster.  The reference
+ * has no counterpart to this stage; the semantics are this library's own.  Every output is a function of the input alone -- the same bits
+ * on every run, whatever the schedule --: integer atomics only, no float atomic, no sum of floats.
+ *
+ * sdfr_lidar_clusters.  points [N][3], device memory, float64 (points_f64 != 0) or float32 (widened first), as sdfr_lidar_normals takes
+ * them.  mask uint8[N] or NULL (every point).  A point TAKES PART if its mask is non-zero and its three coordinates are finite.  Two such
+ * points are NEIGHBOURS if d2 = (dx*dx + dy*dy) + dz*dz < eps*eps, strictly, in float64 (eps is a float32 value, widened).  A COMPONENT
+ * is a connected component of that graph.  A component is a CLUSTER if min_points <= size and (max_points <= 0 or size <= max_points).
+ * Clusters are numbered 0, 1, ... in ascending order of their smallest member index; only the first max_clusters (1 ... 4096) are kept.
+ *   counts int32[4] = participating points, components, clusters found (the true number, capped or not), flags: bit 1 (value 1) the cap
+ *     cut something, bit 2 (value 2) a non-finite point under a set mask was left out.
+ *   label int32[N]: the cluster's number; -1 for a point that takes no part, whose component is no cluster, or whose cluster is beyond the cap.
+ *   off int32[max_clusters + 1]: first member slot of every kept cluster; the entries beyond the kept count equal the total.
+ *   members int32[N]: the input indices cluster by cluster, ascending within a cluster (a stable partition); entries from off[kept] on are
+ *     NOT written.
+ * The components come from a union-find over input indices with parent[i] <= i (every write lowers a value; no loop waits for another
+ * thread; a component's root is its smallest index whatever the order of the unions), over the hash grid of sdfr_lidar_normals.
+ * workspace: sdfr_cluster_ws_bytes(N, max_clusters) bytes of device memory, 16-byte aligned (-1 beyond the limits: N <= 2^24,
+ * max_clusters <= 4096, ceil(N / 1024) * max_clusters <= 2^26).  N == 0: counts and off are zeroed.  No host read, nothing for the caller
+ * to clear, no host synchronisation.
+ *
+ * sdfr_cluster_boxes.  members, off, counts: sdfr_lidar_clusters' (of the same points).  dirs double[K][2] = (cos, sin) of K directions
+ * (1 ... 1024), device memory, made by the caller: no cosine or sine is evaluated on the device.  Per member point and direction, in float64
+ * of the stored coordinates, one rounding per statement: a = x*c; b = z*s; u = a + b; a = z*c; b = x*s; v = a - b.  Per cluster and
+ * direction: the minima and maxima of u and v (a zero is +0), area = (u_max - u_min) * (v_max - v_min); the winner is the first
+ * direction of the smallest area.  rect double[max_clusters][8] = k, u_min, u_max, v_min, v_max, y_min, y_max, area of the winner; rows
+ * beyond the kept count are NOT written.  One launch, no host synchronisation. */
+int64_t sdfr_cluster_ws_bytes(int N, int max_clusters);
+int sdfr_lidar_clusters(const void* points, int points_f64, int N, const uint8_t* mask, float eps, int min_points, int max_points,
+                        int max_clusters, int32_t* label, int32_t* members, int32_t* off, int32_t* counts, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+int sdfr_cluster_boxes(const void* points, int points_f64, int N, const int32_t* members, const int32_t* off, const int32_t* counts,
+                       int max_clusters, const double* dirs, int K, double* rect, void* stream);
 
 /* Debug only: forward kernels of a library built with -DSDFR_MLP_TRACE write cycle stamps of their workgroup 0 into this device buffer
  * (8 waves * SDFR_MAX_LAYERS * 5 uint64; see tools/cycle_trace.py); pass NULL to disable.  Production builds ignore it. */

@@ -1,0 +1,297 @@
+"""Lidar clusters and rough boxes without a GPU: the numpy restatement (tests/_cluster_ref.py) against scipy's connected_components over
+cKDTree pairs, the pose convention of the proposals through the restatement of verify_point_x (tests/_verify_ref.point_x),
+csrc/cluster_cells.h compiled into a host program (tests/cluster_host/cluster_host.cpp) against the restatement bit for bit -- also under
+ASan/UBSan with exact-size buffers; that stand-alone program, not anything loaded into Python, is the sanitizer run --, exports / header /
+binding, the version line, argument checks, and the planted scene, on which the restatement must find exactly the planted objects (so the
+GPU test only has to equal the restatement).
+
+The concurrent union is a device matter: on the host one thread runs after the other.  The host program pins the rules and the index
+arithmetic, with the scatter and the unions walked in both directions.
+"""
+import os
+import re
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from sdflabel_amd import _lib
+from tests import _cluster_ref as CR
+from tests import _verify_ref as VR
+from tests._util import ROOT, build_host_program
+
+NEW = ("sdfr_cluster_ws_bytes", "sdfr_lidar_clusters", "sdfr_cluster_boxes")
+
+
+# ---- the restatement against scipy -------------------------------------------------------------------------------------------------------
+
+def _near_threshold(P, part, eps, tol=1e-9):
+    from scipy.spatial import cKDTree
+    Q = np.asarray(P, np.float64)[part]
+    if len(Q) < 2:
+        return False
+    t = cKDTree(Q)
+    outer, inner = t.query_pairs(eps + tol, output_type="ndarray"), t.query_pairs(eps - tol, output_type="ndarray")
+    return len(outer) != len(inner)
+
+
+def test_restatement_agrees_with_scipy_connected_components():
+    """scipy's test is d <= eps, the rule is d2 < eps^2: a case is admitted only if no pair lies within 1e-9 of eps, and only the two crafted
+    threshold cases may be left out"""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    from scipy.spatial import cKDTree
+    left_out = []
+    for name, case in CR.cluster_cases().items():
+        P, kw = case["points"], case["kw"]
+        part, _ = CR.takes_part(P, case["mask"])
+        if _near_threshold(P, part, kw["eps"]):
+            left_out.append(name)
+            continue
+        ref = CR.cluster_refs()[name]
+        idx = np.nonzero(part)[0]
+        n = len(idx)
+        pr = cKDTree(np.asarray(P, np.float64)[idx]).query_pairs(kw["eps"], output_type="ndarray") if n else np.zeros((0, 2), np.int64)
+        ncomp, lab = connected_components(coo_matrix((np.ones(len(pr)), (pr[:, 0], pr[:, 1])), shape=(n, n)), directed=False) if n else (0, np.zeros(0, int))
+        assert ncomp == ref["counts"][1], name
+        root = ref["root"][idx]
+        # the same partition: one scipy label per root and one root per scipy label
+        assert len(set(zip(lab.tolist(), root.tolist()))) == ncomp, name
+        for r in np.unique(root):
+            assert r == idx[root == r].min(), name                         # the root is the smallest member index
+    assert sorted(left_out) == sorted(CR.THRESHOLD_CASES), left_out
+
+
+def test_restatement_rules_on_the_crafted_cases():
+    refs, cases = CR.cluster_refs(), CR.cluster_cases()
+    assert refs["exactly_eps_apart"]["counts"].tolist() == [2, 2, 2, 0] and refs["just_below_eps"]["counts"].tolist() == [2, 1, 1, 0]
+    assert refs["chain"]["counts"].tolist() == [3000, 1, 1, 0] and (refs["chain"]["members"] == np.arange(3000)).all()
+    assert refs["identical"]["counts"].tolist() == [300, 1, 1, 0]
+    assert refs["far_cells"]["counts"][1] == 400
+    assert refs["masked_bridge"]["counts"].tolist() == [80, 2, 2, 0] and refs["open_bridge"]["counts"].tolist() == [81, 1, 1, 0]
+    assert refs["masked_bridge"]["label"][40] == -1
+    assert refs["nonfinite"]["counts"].tolist() == [80, 2, 2, CR.NONFINITE] and refs["nonfinite_masked_out"]["counts"][3] == 0
+    assert refs["min_points_edge"]["counts"].tolist() == [30, 3, 2, 0] and np.diff(refs["min_points_edge"]["off"][:3]).tolist() == [10, 11]
+    assert refs["max_points_edge"]["counts"].tolist() == [60, 3, 2, 0] and sorted(np.diff(refs["max_points_edge"]["off"][:3]).tolist()) == [19, 20]
+    assert refs["exactly_max_clusters"]["counts"].tolist() == [64, 16, 16, 0]
+    over = refs["one_over_max_clusters"]
+    assert over["counts"].tolist() == [68, 17, 17, CR.CAPPED] and over["kept"] == 16 and (over["label"] == -1).sum() == 4 and over["off"][16] == 64
+    assert refs["n0"]["counts"].tolist() == [0, 0, 0, 0] and not refs["n0"]["off"].any()
+    assert refs["all_masked_out"]["counts"].tolist() == [0, 0, 0, 0] and (refs["all_masked_out"]["label"] == -1).all()
+    assert cases["float64_input"]["points"].dtype == np.float64 and cases["n65"]["points"].dtype == np.float32
+    for name, ref in refs.items():                                         # numbering by smallest member, members ascending within a cluster
+        firsts = [ref["members"][ref["off"][c]] for c in range(ref["kept"])]
+        assert firsts == sorted(firsts), name
+        for c in range(ref["kept"]):
+            m = ref["members"][ref["off"][c]:ref["off"][c + 1]]
+            assert (np.diff(m) > 0).all() and (ref["label"][m] == c).all(), name
+    cl, rect = CR.box_refs()["tie_first_wins"]
+    assert rect[0, 0] == 1 and rect[0, 7] == 4.0                            # rows 1, 3 and 4 of the table tie; the first wins
+    cl, rect = CR.box_refs()["single_point"]
+    assert (rect[:, 7] == 0).all() and (rect[:, 1] == rect[:, 2]).all()
+    cl, rect = CR.box_refs()["rotated"]
+    assert len(rect) == 3 and (rect[:, 7] < 8.0).all()                      # 4.2 x 1.8 slabs: the rotation is found (13.5 without, 'one_direction')
+    assert (CR.box_refs()["one_direction"][1][:, 7] > 10).all()
+
+
+def test_permuting_the_points_keeps_the_components_and_renumbers_them():
+    case = CR.cluster_cases()["n1025"]
+    ref = CR.cluster_refs()["n1025"]
+    perm = np.random.default_rng(3).permutation(1025)
+    got = CR.clusters(case["points"][perm], None, **case["kw"])
+    sets = lambda r, p: sorted(tuple(sorted(p[r["members"][r["off"][c]:r["off"][c + 1]]].tolist())) for c in range(r["kept"]))       # noqa: E731
+    assert sets(got, perm) == sets(ref, np.arange(1025))
+    firsts = [got["members"][got["off"][c]] for c in range(got["kept"])]
+    assert firsts == sorted(firsts)
+
+
+# ---- the pose convention -----------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("yaw_true", (0.0, 0.4, 1.2, -0.7, 2.5, np.pi / 2))
+def test_rectangle_pose_puts_a_planted_box_into_the_cube_with_its_long_side_on_lattice_z(yaw_true):
+    """A box of 3.8 x 1.6 x 1.4 m (length along the lattice z axis) posed by x = diag(1, -1, 1) rot(yaw)^T (p / scale - trans), inverted
+    here by hand; its corners and surface points go through the rectangle search and starts_from_rect, and the resulting pose must take the
+    corners back to +-(0.4, 0.35, 0.95) up to the table's angular step, for both hypotheses yaw and yaw + pi."""
+    from sdflabel_amd.cluster import directions, starts_from_rect
+    scale, trans = 2.0, np.array([1.5, 0.4, 6.0])
+    rng = np.random.default_rng(1)
+    half = np.array([0.4, 0.35, 0.95])                                       # lattice half extents: x width, y height, z length
+    x = np.concatenate([np.array([[a, b, c] for a in (-1, 1) for b in (-1, 1) for c in (-1, 1)]) * half, rng.uniform(-1, 1, (400, 3)) * half])
+    c, s = np.cos(yaw_true), np.sin(yaw_true)
+    # x0 = c q0 - s q2, x1 = -q1, x2 = s q0 + c q2  =>  q0 = c x0 + s x2, q1 = -x1, q2 = -s x0 + c x2
+    q = np.stack([c * x[:, 0] + s * x[:, 2], -x[:, 1], -s * x[:, 0] + c * x[:, 2]], 1)
+    p = ((q + trans) * scale).astype(np.float32)
+    back, inside = VR.point_x(p, VR.pose_row(np.float32(c), np.float32(s), trans, scale))
+    assert inside.all() and np.abs(back - x).max() < 1e-6                   # the hand inversion is verify_point_x's convention
+    cl = {"kept": 1, "members": np.arange(len(p), dtype=np.int32), "off": np.array([0, len(p)], np.int32)}
+    dirs = directions(90)
+    rect = CR.rectangles(p, cl, dirs)
+    yaw, tr, dims = starts_from_rect(rect, dirs, scale)
+    step = (np.pi / 2) / 90
+    assert abs(dims[0, 0] - 3.8) < 0.1 and abs(dims[0, 1] - 1.6) < 0.1 and abs(dims[0, 2] - 1.4) < 1e-6
+    assert np.abs(tr[0] - trans).max() < 0.05
+    d = (yaw[0] - yaw_true + np.pi / 2) % np.pi - np.pi / 2                 # modulo pi: front and back cannot be told apart
+    assert abs(d) <= step + 1e-9, (yaw[0], yaw_true)
+    for flip in (0.0, np.pi):
+        y = np.float32(yaw[0] + flip)
+        got, inside = VR.point_x(p, VR.pose_row(np.float32(np.cos(np.float64(y))), np.float32(np.sin(np.float64(y))), tr[0], scale))
+        assert inside.all()
+        ext = np.abs(got[:8].astype(np.float64))
+        assert np.abs(ext - half).max() < 1.0 * np.sin(step) + 0.03, ext      # a corner moves by at most |z| sin(step), plus the centre's error
+        assert ext[:, 2].max() > 0.85 > ext[:, 0].max()                       # the long side lies on lattice z
+
+
+# ---- the host build of the cells header ------------------------------------------------------------------------------------------------
+
+def _run_host(exe, tmp, case, dirs, reverse):
+    P, kw = case["points"], case["kw"]
+    N, C, K = len(P), kw["max_clusters"], len(dirs)
+    mask = case["mask"]
+    head = struct.pack("<8if", N, int(P.dtype == np.float64), int(mask is not None), kw["min_points"], kw["max_points"] or 0, C, K, reverse,
+                       np.float32(kw["eps"]))
+    src, dst = os.path.join(str(tmp), "in.bin"), os.path.join(str(tmp), "out.bin")
+    with open(src, "wb") as f:
+        f.write(head + np.ascontiguousarray(P).tobytes() + (b"" if mask is None else mask.tobytes()) + np.ascontiguousarray(dirs, np.float64).tobytes())
+    r = subprocess.run([exe, src, dst], capture_output=True, text=True)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    raw = open(dst, "rb").read()
+    i32 = np.frombuffer(raw[:4 * (2 * N + C + 5)], np.int32)
+    rect = np.frombuffer(raw[4 * (2 * N + C + 5):], np.float64).reshape(C, 8)
+    return i32[:N], i32[N:2 * N], i32[2 * N:2 * N + C + 1], i32[2 * N + C + 1:], rect
+
+
+def _bits(a, b, what):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), what
+
+
+def _host_checks(exe, tmp):
+    todo = [(n, c, CR.directions(7), CR.cluster_refs()[n], None) for n, c in CR.cluster_cases().items()]
+    todo += [(n, c, c["dirs"]) + CR.box_refs()[n] for n, c in CR.box_cases().items()]
+    for name, case, dirs, ref, rect in todo:
+        rect = CR.rectangles(case["points"], ref, dirs) if rect is None else rect
+        for reverse in (0, 1):
+            label, members, off, counts, got = _run_host(exe, tmp, case, dirs, reverse)
+            total, kept = int(ref["off"][ref["kept"]]), ref["kept"]
+            _bits(label, ref["label"], name); _bits(off, ref["off"], name); _bits(counts, ref["counts"], name)
+            _bits(members[:total], ref["members"], name)
+            assert (members[total:] == -7).all() and (got[kept:] == -7.0).all(), name      # what must stay unwritten
+            _bits(got[:kept], rect, name)
+
+
+def test_cluster_cells_on_the_host_equal_the_restatement_bit_for_bit(tmp_path):
+    _host_checks(build_host_program(tmp_path, "cluster_host/cluster_host.cpp", "cluster_host"), tmp_path)
+
+
+def test_cluster_cells_host_program_under_sanitizers(tmp_path):
+    _host_checks(build_host_program(tmp_path, "cluster_host/cluster_host.cpp", "cluster_host_san",
+                                    ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]), tmp_path)
+
+
+# ---- exports, header, binding, argument checks -------------------------------------------------------------------------------------------
+
+def test_exports_header_and_binding_agree():
+    """fails before the feature: the ABI has no cluster entry points"""
+    header = open(os.path.join(ROOT, "include", "sdfr.h")).read()
+    assert int(re.search(r"#define SDFR_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION >= 421
+    assert "421: lidar clusters and rough boxes, sdfr_cluster_*" in header and "420: pose and shape fitted to one view" in header
+    body = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    h = _lib.lib()
+    assert h.sdfr_version() == _lib.ABI_VERSION
+    for name in NEW:
+        assert name in _lib.EXPORTS and hasattr(h, name), name
+        args = re.search(r"\bint(?:64_t)? %s\((.*?)\);" % name, body, flags=re.S).group(1)
+        assert len(args.split(",")) == len(_lib._PROTOS[name][1]), name
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("sdfr_")}
+    declared = set(re.findall(r"\b(sdfr_\w+)\s*\(", body))
+    assert exported == declared == set(_lib.EXPORTS)
+    cells = open(os.path.join(ROOT, "sdflabel_amd", "csrc", "cluster_cells.h")).read()
+    from sdflabel_amd import cluster as C
+    for name, val in (("CLU_FLAG_CAPPED", CR.CAPPED), ("CLU_FLAG_NONFINITE", CR.NONFINITE), ("CLU_RECT", CR.RECT), ("CLU_MAX_CLUSTERS", C.MAX_CLUSTERS)):
+        assert int(re.search(r"#define %s (\d+)" % name, cells).group(1)) == val, name
+    assert (C.CAPPED, C.NONFINITE) == (CR.CAPPED, CR.NONFINITE)
+    build = open(os.path.join(ROOT, "sdflabel_amd", "csrc", "build.sh")).read()
+    assert re.search(r"-ffp-contract=off -c \"\$HERE/cluster.hip\"", build)
+    unit = open(os.path.join(ROOT, "sdflabel_amd", "csrc", "cluster.hip")).read()
+    assert "cluster_cells.h" in unit and "atomicAdd(float" not in unit and "parent[i] <= i" in unit
+    assert np.array_equal(C.directions(90), CR.directions(90))
+
+
+def test_c_argument_checks_need_no_gpu():
+    h = _lib.lib()
+    d, inv = 4096, -1            # never dereferenced: every call below is refused before a launch
+    assert 0 < h.sdfr_cluster_ws_bytes(0, 16) < h.sdfr_cluster_ws_bytes(1000, 16) < h.sdfr_cluster_ws_bytes(120000, 16) < h.sdfr_cluster_ws_bytes(120000, 512)
+    assert h.sdfr_cluster_ws_bytes(-1, 16) == -1 and h.sdfr_cluster_ws_bytes(10, 0) == -1 and h.sdfr_cluster_ws_bytes(10, 4097) == -1
+    assert h.sdfr_cluster_ws_bytes((1 << 24) + 1, 16) == -1 and h.sdfr_cluster_ws_bytes(1 << 24, 4096) > 0 and h.sdfr_cluster_ws_bytes(1 << 24, 4096) % 16 == 0
+    big = h.sdfr_cluster_ws_bytes(1000, 16)
+    assert h.sdfr_lidar_clusters(d, 0, -1, None, 0.5, 10, 0, 16, d, d, d, d, d, big, None) == inv and b"point count" in h.sdfr_last_error()
+    assert h.sdfr_lidar_clusters(d, 0, 1000, None, 0.5, 10, 0, 0, d, d, d, d, d, big, None) == inv and b"max_clusters" in h.sdfr_last_error()
+    assert h.sdfr_lidar_clusters(d, 0, 1000, None, 0.0, 10, 0, 16, d, d, d, d, d, big, None) == inv and b"eps" in h.sdfr_last_error()
+    assert h.sdfr_lidar_clusters(d, 0, 1000, None, float("inf"), 10, 0, 16, d, d, d, d, d, big, None) == inv and b"eps" in h.sdfr_last_error()
+    assert h.sdfr_lidar_clusters(None, 0, 1000, None, 0.5, 10, 0, 16, d, d, d, d, d, big, None) == inv and b"NULL" in h.sdfr_last_error()
+    assert h.sdfr_lidar_clusters(d, 0, 1000, None, 0.5, 10, 0, 16, d, d, None, d, d, big, None) == inv and b"NULL" in h.sdfr_last_error()
+    assert h.sdfr_lidar_clusters(d, 0, 1000, None, 0.5, 10, 0, 16, d, d, d, d, d + 8, big, None) == inv and b"aligned" in h.sdfr_last_error()
+    assert h.sdfr_lidar_clusters(d, 0, 1000, None, 0.5, 10, 0, 16, d, d, d, d, d, big - 1, None) == inv and b"sdfr_cluster_ws_bytes" in h.sdfr_last_error()
+    assert h.sdfr_cluster_boxes(d, 0, 1000, d, d, d, 16, d, 0, d, None) == inv and b"direction" in h.sdfr_last_error()
+    assert h.sdfr_cluster_boxes(d, 0, 1000, d, d, d, 16, d, 1025, d, None) == inv and b"direction" in h.sdfr_last_error()
+    assert h.sdfr_cluster_boxes(d, 0, 1000, d, d, d, 4097, d, 90, d, None) == inv and b"max_clusters" in h.sdfr_last_error()
+    assert h.sdfr_cluster_boxes(d, 0, 1000, d, d, d, 16, None, 90, d, None) == inv and b"NULL" in h.sdfr_last_error()
+    assert h.sdfr_cluster_boxes(None, 0, 0, None, None, None, 16, None, 90, None, None) == 0
+
+
+def test_python_argument_checks_and_no_cpu_fallback(monkeypatch):
+    from sdflabel_amd import cluster as C
+    from sdflabel_amd.pipelines import scan
+    P = torch.from_numpy(np.array(CR.cluster_cases()["n65"]["points"]))
+    for bad in (dict(eps=0.0), dict(eps=float("nan")), dict(max_clusters=0), dict(max_clusters=4097)):
+        with pytest.raises(ValueError):
+            C.clusters(P, **bad)
+    with pytest.raises(ValueError):
+        C.directions(0)
+    with pytest.raises(ValueError):
+        C.directions(1025)
+    with pytest.raises(ValueError, match="latent is required"):
+        C.proposals(P)
+    with pytest.raises(ValueError):
+        C.proposals(P, latent=np.zeros(3), scale=0.0)
+    with pytest.raises(ValueError):
+        C.proposals(P, latent=np.zeros(3), gates={"depth": (0, 1)})
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)              # host inputs and no GPU: a loud refusal, never a host computation
+    with pytest.raises(_lib.SdfrError):
+        C.clusters(P)
+    with pytest.raises(_lib.SdfrError):
+        C.proposals(P, latent=np.zeros(3))
+    with pytest.raises(_lib.SdfrError):
+        scan.label_scan(None, None, P, np.eye(3), 8, 8, np.eye(4), np.zeros(3), remove_road=False)
+    assert "WITHOUT A CLAIMED OPERATING POINT" in C.__doc__ and "ONE HOST READ" in C.proposals.__doc__
+    assert "HOST SYNCHRONISATIONS" in scan.label_scan.__doc__ and "no counterpart" in C.__doc__
+
+
+# ---- the planted scene ------------------------------------------------------------------------------------------------------------------
+
+def test_restatement_finds_exactly_the_planted_objects():
+    from sdflabel_amd.cluster import starts_from_rect
+    sc, s = CR.planted_scene(), CR.SCENE
+    P, owner = sc["points"], sc["owner"]
+    cl = CR.clusters(P, sc["mask"], eps=s["eps"], min_points=s["min_points"], max_clusters=64)
+    dirs = CR.directions(s["n_angles"])
+    rect = CR.rectangles(P, cl, dirs)
+    yaw, trans, dims = starts_from_rect(rect, dirs, s["scale"])
+    g = np.array([s["gates"][k] for k in ("length", "width", "height")])
+    ok = np.nonzero(((dims >= g[:, 0]) & (dims <= g[:, 1])).all(1))[0]
+    print("planted scene: %d points, %d take part, %d components, %d clusters, %d pass the gates; dims %s" %
+          (len(P), cl["counts"][0], cl["counts"][1], cl["counts"][2], len(ok), np.round(dims, 2).tolist()))
+    assert cl["counts"][3] == 0 and cl["kept"] == 4 and len(ok) == 3         # three objects and the wall; the gates reject the wall
+    found = set()
+    for c in range(cl["kept"]):
+        m = cl["members"][cl["off"][c]:cl["off"][c + 1]]
+        who = np.unique(owner[m])
+        # a cluster is one planted thing and nothing else, and all of it but camera-facing vertices that lie alone (under 1 %)
+        assert len(who) == 1 and 0.99 * (owner == who[0]).sum() <= len(m)
+        assert (who[0] >= 0) == (c in ok)
+        found.add(int(who[0]))
+    assert found == {0, 1, 2, -2}
+    assert (cl["label"][owner == -1] == -1).all() and (cl["label"][owner == -3] == -1).all()      # the ground is masked, the strays are too few
