@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 421        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 422        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -50,7 +50,8 @@ extern "C" {
  * builds, sdfr_debug_set_tile_trace; 417: training the decoder, sdfr_decoder_train_*; 418: encoding shapes under a
  * frozen decoder, sdfr_encode_*; 419: shape completion from one view, sdfr_view_samples and
  * sdfr_bound_*; 420: pose and shape fitted to one view, sdfr_align_*;
- * 421: lidar clusters and rough boxes, sdfr_cluster_* and sdfr_lidar_clusters).  A caller built
+ * 421: lidar clusters and rough boxes, sdfr_cluster_* and sdfr_lidar_clusters; 422: band selection and tile ranking in one launch,
+ * sdfr_mlp_forward_balanced_deferred and sdfr_band_select_rank).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -126,6 +127,12 @@ int64_t sdfr_mlp_balance_bytes(int64_t order_rows);
 int sdfr_mlp_balance_init(void* state, const int32_t* order, int64_t order_rows, void* stream);
 int sdfr_mlp_forward_balanced(const sdfr_decoder* dec, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, void* state,
                               int64_t order_rows, void* stream);
+/* sdfr_mlp_forward_balanced without its ranking launch (SDFR_VERSION 422): same arguments, same checks, the tiles still add their costs to
+ * `state`; the ranking is left to the sdfr_band_select_rank that follows.  One launch.  A forward that runs twice without a ranking between
+ * adds the costs of both passes: the next order is then ranked by the sums and is still a permutation (every entry of it is written from the
+ * state's static order). */
+int sdfr_mlp_forward_balanced_deferred(const sdfr_decoder* dec, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, void* state,
+                                       int64_t order_rows, void* stream);
 /* sdfr_mlp_forward with float16 operands on the matrix cores (weights and hidden activations rounded to half, float32 accumulation, bias,
  * ReLU and tanh) -- the decoder precision of the reference's default config (configs/config_refine.ini:19); inputs/outputs stay float32. */
 int sdfr_mlp_forward_f16(const sdfr_decoder* dec, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, void* stream);
@@ -495,6 +502,17 @@ int sdfr_params_plan(const float* yaw, const float* trans, const float* latent, 
  * skip, slot and over may be NULL.  Launches of up to 8 crops with a flag array take one workgroup per crop (one launch instead of two). */
 int sdfr_band_select_ex(const float* sdf, int64_t G, int B, float thr, const float* thr_extra, const int32_t* skip, int32_t* idx, int cap,
                         int32_t* cnt, int32_t* slot, int32_t* scratch, int32_t* over, int over_bit, void* stream);
+/* sdfr_band_select_ex and the ranking of sdfr_mlp_forward_balanced in ONE launch (SDFR_VERSION 422), for the serial stretch between a
+ * one-crop grid forward and the band's Jacobian.  Selection: idx / cnt / slot / over receive what sdfr_band_select_ex writes (ascending grid
+ * order, cap, thr_extra, skip, the sticky bit); there is no scratch -- a workgroup of 1024 rows counts the band rows of its crop in front of
+ * its own straight from sdf, redundant reads that grow with B G^2, instead of a counting launch.  No workgroup waits for another.
+ * balance_state / order_rows: the state of sdfr_mlp_forward_balanced_deferred, ranked by further workgroups of the same launch exactly as
+ * sdfr_mlp_forward_balanced ranks it (orders of more than 4096 chunks: not ranked); NULL: the selection alone.  One kernel, no memset or copy
+ * node.  sdfr_band_select_rank_max_rows(): the B G up to which this launch is the faster form (measured, profiles/chain_notes.md); callers keep
+ * sdfr_mlp_forward_balanced + sdfr_band_select_ex above it. */
+int sdfr_band_select_rank(const float* sdf, int64_t G, int B, float thr, const float* thr_extra, const int32_t* skip, int32_t* idx, int cap,
+                          int32_t* cnt, int32_t* slot, int32_t* over, int over_bit, void* balance_state, int64_t order_rows, void* stream);
+int64_t sdfr_band_select_rank_max_rows(void);
 /* sdfr_candidate_rows + sdfr_mlp_forward(_f16)_ragged without the gathered copy: row s < cnt[b] of crop b is
  * inputs[b * rows_per_crop_in + cidx[b][s]]; values -> sdf [B][stride], masks -> mask_ws.  half: the float16 kernel (half_tiles: 64-row
  * tiles); else the exact-float32 kernel.  stride a multiple of the tile (128 / 64).  (deep_sdf_decoder_scale.py:78-107 on the candidate rows) */

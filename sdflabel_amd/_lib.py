@@ -9,7 +9,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDFR_LIB") or os.path.join(_HERE, "lib", "libsdfr_hip.so")     # SDFR_LIB: A/B builds (tools/ab_build.sh)
 
-ABI_VERSION = 421          # include/sdfr.h SDFR_VERSION
+ABI_VERSION = 422          # include/sdfr.h SDFR_VERSION
 _lib = None
 
 # name -> (restype, argtypes); mirrors include/sdfr.h one to one
@@ -81,6 +81,7 @@ _PROTOS = {
     "sdfr_mlp_balance_bytes": (c_int64, [c_int64]),
     "sdfr_mlp_balance_init": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "sdfr_mlp_forward_balanced": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sdfr_mlp_forward_balanced_deferred": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sdfr_mlp_forward_f16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sdfr_mlp_forward_f16_counted": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdfr_mlp_forward_split": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
@@ -154,6 +155,9 @@ _PROTOS = {
                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "sdfr_band_select_ex": (c_int, [c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int, c_void_p]),
+    "sdfr_band_select_rank": (c_int, [c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_int64, c_void_p]),
+    "sdfr_band_select_rank_max_rows": (c_int64, []),
     "sdfr_mlp_forward_candidates": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                             c_void_p]),
     "sdfr_candidate_band": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p,

@@ -84,6 +84,7 @@ class BatchRenderer:
             self.fwd_balance = torch.empty(int(lib.sdfr_mlp_balance_bytes(self.G)) // 4, dtype=torch.int32, device=dev)
             with _lib.guard(dev):                           # (a launch: the renderer's device must be current, as in forward())
                 ck(lib.sdfr_mlp_balance_init(P(self.fwd_balance), P(self.fwd_order), self.G, _lib.stream_ptr()), "sdfr_mlp_balance_init")
+            self.band_rank_max_rows = int(lib.sdfr_band_select_rank_max_rows())
         self.cap = int(cap) if cap is not None else max(256, self.G // 8)       # surfel capacity per crop
         self._init_extents(K, max_pixels, max_side)
         self._alloc_common()
@@ -423,7 +424,14 @@ class BatchRenderer:
         """the mode's kernel over the whole grid (values + ReLU masks) -> band -> mask-fed Jacobian of the band rows"""
         B, G, cap = self.B, self.G, self.cap
         fwd = L.sdfr_mlp_forward_f16 if self.f16 else (L.sdfr_mlp_forward_split if self.split else L.sdfr_mlp_forward)
-        if self.fwd_order is not None and os.environ.get("SDFR_FWD_ORDER", "1") != "0" and os.environ.get("SDFR_FWD_BALANCE", "1") != "0":
+        balanced = self.fwd_order is not None and os.environ.get("SDFR_FWD_ORDER", "1") != "0" and os.environ.get("SDFR_FWD_BALANCE", "1") != "0"
+        # the ranking behind the balanced forward and the band selection in ONE launch (csrc/band_rank.hip) where its redundant count is
+        # cheaper than the launches it replaces; SDFR_BAND_FUSED=0, read at every launch, selects the separate launches.  Same bits.
+        rank_fused = balanced and B * G <= self.band_rank_max_rows and os.environ.get("SDFR_BAND_FUSED", "1") != "0"
+        if rank_fused:
+            ck(L.sdfr_mlp_forward_balanced_deferred(self.handle.h, P(self.inputs), B * G, P(self.sdf), P(self.mask_ws), P(self.fwd_balance), G, st),
+               "sdfr_mlp_forward_balanced_deferred")
+        elif balanced:
             ck(L.sdfr_mlp_forward_balanced(self.handle.h, P(self.inputs), B * G, P(self.sdf), P(self.mask_ws), P(self.fwd_balance), G, st),
                "sdfr_mlp_forward_balanced")
         elif self.fwd_order is not None and os.environ.get("SDFR_FWD_ORDER", "1") != "0":
@@ -433,8 +441,12 @@ class BatchRenderer:
             ck(fwd(self.handle.h, P(self.inputs), B * G, P(self.sdf), P(self.mask_ws), st), fwd.__name__)
         if mlp_events is not None:
             mlp_events[1].record()
-        ck(L.sdfr_band_select_ex(P(self.sdf), G, B, self.thr, None, None, P(self.idx), cap, P(self.cnt), None, P(self.scratch), P(self.over), 1, st),
-           "sdfr_band_select_ex")
+        if rank_fused:
+            ck(L.sdfr_band_select_rank(P(self.sdf), G, B, self.thr, None, None, P(self.idx), cap, P(self.cnt), None, P(self.over), 1,
+                                       P(self.fwd_balance), G, st), "sdfr_band_select_rank")
+        else:
+            ck(L.sdfr_band_select_ex(P(self.sdf), G, B, self.thr, None, None, P(self.idx), cap, P(self.cnt), None, P(self.scratch), P(self.over), 1,
+                                     st), "sdfr_band_select_ex")
         if "jacobian" in events:
             events["jacobian"][0].record()
         ck(L.sdfr_mlp_jacobian(self.handle.h, P(self.inputs), G, B, P(self.idx), cap, P(self.cnt), P(self.J), P(self.sdf_band), P(self.sdf),

@@ -37,6 +37,7 @@ $HIPCC $COMMON -c "$HERE/mlp_balance.hip" -o "$HERE/obj/mlp_balance.o" &
 $HIPCC $COMMON -c "$HERE/mlp_small.hip" -o "$HERE/obj/mlp_small.o" &
 $HIPCC $COMMON -c "$HERE/mlp_ln.hip"    -o "$HERE/obj/mlp_ln.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/surface.hip" -o "$HERE/obj/surface.o" &
+$HIPCC $COMMON -ffp-contract=off -c "$HERE/band_rank.hip" -o "$HERE/obj/band_rank.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/project.hip" -o "$HERE/obj/project.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/splat.hip"   -o "$HERE/obj/splat.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/params.hip"  -o "$HERE/obj/params.o" &
@@ -62,5 +63,5 @@ $HIPCC $COMMON -ffp-contract=off -c "$HERE/complete.hip" -o "$HERE/obj/complete.
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/align.hip" -o "$HERE/obj/align.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/cluster.hip" -o "$HERE/obj/cluster.o" &
 wait
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/${SDFR_LIBNAME:-libsdfr_hip.so}" "$HERE"/obj/{common,mlp,mlp_fwd32,mlp_fwd16,mlp_split,mlp_jac,mlp_jac16,mlp_persist,mlp_balance,mlp_small,mlp_ln,mlp_train,encode,complete,align,cluster,surface,project,splat,params,losses,trace,pose,box_iou,detection_eval,frame,ingest,augment,normals,css_head,css_train,mesh,verify,crops,synth,mesh_sdf}.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/${SDFR_LIBNAME:-libsdfr_hip.so}" "$HERE"/obj/{common,mlp,mlp_fwd32,mlp_fwd16,mlp_split,mlp_jac,mlp_jac16,mlp_persist,mlp_balance,mlp_small,mlp_ln,mlp_train,encode,complete,align,cluster,surface,band_rank,project,splat,params,losses,trace,pose,box_iou,detection_eval,frame,ingest,augment,normals,css_head,css_train,mesh,verify,crops,synth,mesh_sdf}.o
 echo "built $OUT/${SDFR_LIBNAME:-libsdfr_hip.so}"

@@ -164,7 +164,7 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
         SDFR_HIP_CHECK(hipMalloc(&d->d_Wkj, Wkj.size() * sizeof(float)));
         SDFR_HIP_CHECK(hipMemcpy(d->d_Wkj, Wkj.data(), Wkj.size() * sizeof(float), hipMemcpyHostToDevice));
         P.Wkj = d->d_Wkj;
-        P.jcompact = finite ? 1 : 0;
+        P.jcompact = finite ? 2 : 0;
     }
     P.Wf = d->d_Wf; P.Wb = d->d_Wb; P.Wh = d->d_Wh; P.Ws = d->d_Ws; P.Wbh = d->d_Wbh; P.bias = d->d_bias; P.w_last = d->d_wlast; P.fwd_np = 2;
     *out = d;
@@ -291,17 +291,19 @@ extern "C" int sdfr_mlp_balance_init(void* state, const int32_t* order, int64_t 
     return SDFR_OK;
 }
 
-extern "C" int sdfr_mlp_forward_balanced(const sdfr_decoder* d, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, void* state,
-                                         int64_t order_rows, void* stream) {
-    SDFR_REQUIRE(d && inputs && sdf && state, "sdfr_mlp_forward_balanced: NULL argument");
-    SDFR_REQUIRE(n >= 0 && n < (int64_t)1 << 31, "sdfr_mlp_forward_balanced: n=%lld out of range", (long long)n);
-    SDFR_REQUIRE(order_rows > 0, "sdfr_mlp_forward_balanced: order_rows=%lld must be positive", (long long)order_rows);
-    SDFR_REQUIRE(n % order_rows == 0, "sdfr_mlp_forward_balanced: n=%lld is not a multiple of order_rows=%lld", (long long)n, (long long)order_rows);
-    SDFR_REQUIRE(d->HP == 512 && !d->has_ln, "sdfr_mlp_forward_balanced: needs a float32 decoder of padded width 512 without LayerNorm (this one: %d%s)",
+// (who: the entry point's name for the messages; rank: the ranking launch behind the forward -- the deferred form leaves it to
+// sdfr_band_select_rank, band_rank.hip)
+static int forward_balanced_impl(const char* who, bool rank, const sdfr_decoder* d, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws,
+                                 void* state, int64_t order_rows, void* stream) {
+    SDFR_REQUIRE(d && inputs && sdf && state, "%s: NULL argument", who);
+    SDFR_REQUIRE(n >= 0 && n < (int64_t)1 << 31, "%s: n=%lld out of range", who, (long long)n);
+    SDFR_REQUIRE(order_rows > 0, "%s: order_rows=%lld must be positive", who, (long long)order_rows);
+    SDFR_REQUIRE(n % order_rows == 0, "%s: n=%lld is not a multiple of order_rows=%lld", who, (long long)n, (long long)order_rows);
+    SDFR_REQUIRE(d->HP == 512 && !d->has_ln, "%s: needs a float32 decoder of padded width 512 without LayerNorm (this one: %d%s)", who,
                  d->HP, d->has_ln ? ", LayerNorm" : "");
     SDFR_REQUIRE(!mask_ws || ((n + 127) / 128) * 128 * (int64_t)(d->n_lin - 1) < (int64_t)1 << 31,
-                 "sdfr_mlp_forward_balanced: n=%lld rows with masks of %d layers exceed the kernel's line index", (long long)n, d->n_lin - 1);
-    SDFR_DEVICE_CHECK(d, "sdfr_mlp_forward_balanced");
+                 "%s: n=%lld rows with masks of %d layers exceed the kernel's line index", who, (long long)n, d->n_lin - 1);
+    SDFR_DEVICE_CHECK(d, who);
     if (n == 0) return SDFR_OK;
     int32_t* st = (int32_t*)state;
     const bool ranked = sdfr_tb_ranked(order_rows);          // (larger orders: tens of rounds, nothing to gain -- the static order, no ranking)
@@ -312,11 +314,24 @@ extern "C" int sdfr_mlp_forward_balanced(const sdfr_decoder* d, const float* inp
     P.tile_at = st + sdfr_tb_at_word(order_rows);
     sdfr_launch_fwd_f32_512_ordered(P, n, st + sdfr_tb_order_word(order_rows), order_rows, (hipStream_t)stream);
     SDFR_LAUNCH_CHECK();
-    if (ranked) {
+    if (ranked && rank) {
         sdfr_launch_tile_balance(st, order_rows, (hipStream_t)stream);
         SDFR_LAUNCH_CHECK();
     }
     return SDFR_OK;
+}
+
+extern "C" int sdfr_mlp_forward_balanced(const sdfr_decoder* d, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, void* state,
+                                         int64_t order_rows, void* stream) {
+    return forward_balanced_impl("sdfr_mlp_forward_balanced", true, d, inputs, n, sdf, mask_ws, state, order_rows, stream);
+}
+
+// The balanced forward WITHOUT the ranking launch: the tiles still add their costs, and the ranking runs in the launch that selects the band
+// (sdfr_band_select_rank).  A forward that runs twice without a ranking between adds both passes' costs; the order stays a valid permutation
+// (every entry is written from fixed[]).
+extern "C" int sdfr_mlp_forward_balanced_deferred(const sdfr_decoder* d, const float* inputs, int64_t n, float* sdf, uint32_t* mask_ws, void* state,
+                                                  int64_t order_rows, void* stream) {
+    return forward_balanced_impl("sdfr_mlp_forward_balanced_deferred", false, d, inputs, n, sdf, mask_ws, state, order_rows, stream);
 }
 
 #ifndef SDFR_COUNTED_TILE16_ROWS

@@ -55,6 +55,10 @@ void sdfr_launch_jac_f32_512(const MlpParams& P, int cap, int B, bool from_masks
         MlpParams Q = P;
         const char* e = getenv("SDFR_JAC_COMPACT");
         if (e && e[0] == '0') Q.jcompact = 0;
+        // SDFR_JAC_STAGE=0 (read at every launch): a survivor's place from the running count over the registers instead of the chain-order words
+        // (kcjd_slots.h) -- the same places, the same bits
+        const char* st = getenv("SDFR_JAC_STAGE");
+        if (st && st[0] == '0' && Q.jcompact) Q.jcompact = 1;
         hipLaunchKernelGGL((sdfr_mlp_kernel<float, 16, SDFR_JAC_SMALL_FT, 1, SDFR_JAC_SMALL_NW, SDFR_JAC_SMALL_PF, 3>), dim3(sdfr_cdiv(cap, 16), B),
                            dim3(64 * SDFR_JAC_SMALL_NW), 0, s, Q);
     }

@@ -24,6 +24,7 @@
 #include "sdfr_common.h"
 #include "kc_slots.h"
 #include "kcj_slots.h"
+#include "kcjd_slots.h"
 #include "tile_balance.h"
 #include <math.h>
 #include <type_traits>
@@ -117,7 +118,8 @@ struct MlpParams {
     unsigned long long* t_evals; // += active rays per pass (ray evaluations of the march, for the roofline)
     int32_t* t_unresolved;       // += rays still active when the step budget ran out
     const float* Wkj;            // exact-f32 backward, k-major image: [layer][k][sdfr_kcj_col(in-feature)] floats at float offset 4 * off_b (KCJ below)
-    int jcompact;                // 1: the 16-row mask-fed Jacobian skips features whose mask bit is 0 in every row of a tile (0: the full K chain)
+    int jcompact;                // != 0: the 16-row mask-fed Jacobian skips features whose mask bit is 0 in every row of a tile (0: the full K chain);
+                                 // 2: a survivor's place from the chain-order words of kcjd_slots.h, 1: from the running count (SDFR_JAC_STAGE=0)
     int32_t* tile_cost;          // ORDER kernels: NULL, or [sdfr_tb_chunks(gather_rows)] costs (tile_balance.h): each tile adds the K extent its
     const int32_t* tile_at;      // compacted products walked to the word of the chunk it evaluates, tile_at[its place in the order]
                                  // (sdfr_mlp_forward_balanced)
@@ -1559,7 +1561,8 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
     // of each lane group with DPP row steps: kcj_w[g] bit q.  The masks do not depend on the product, so the vote runs in front of the barrier
     // that follows it anyway and publishes the wave's count there, as the forward publishes kc_cnt.
     const bool kcj_on = KCJ && P.jcompact && P.Wkj;
-    uint32_t kcj_w[4] = {0u, 0u, 0u, 0u};
+    const bool kcj_fast = P.jcompact >= 2;              // the survivors in chain order as well (kcjd_slots.h): kcj_c[j] bit 4 (q % 8) + g = kcj_w[g] bit 8 j + q % 8
+    uint32_t kcj_w[4] = {0u, 0u, 0u, 0u}, kcj_c[4] = {0u, 0u, 0u, 0u};
     int kcj_n = 0;                                      // compacted K extent of the operand the next product reads
     auto kcj_vote = [&](int l, const uint32_t* raw) {
         const int prev_out = P.L[l - 1].out_dim;
@@ -1582,6 +1585,14 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
         x |= __builtin_amdgcn_update_dpp(0, x, 0x128, 0xf, 0xf, false);     // row_ror:8
 #pragma unroll
         for (int g = 0; g < 4; ++g) kcj_w[g] = (uint32_t)__builtin_amdgcn_readlane(x, 16 * g);
+        if (kcj_fast) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int part = (int)sdfr_kcjd_group_part((uint32_t)x, j, lg);       // (every lane of a lane group holds the group's word)
+                kcj_c[j] = (uint32_t)(__builtin_amdgcn_readlane(part, 0) | __builtin_amdgcn_readlane(part, 16) | __builtin_amdgcn_readlane(part, 32) |
+                                      __builtin_amdgcn_readlane(part, 48));
+            }
+        }
         if (lane == 0) reinterpret_cast<int*>(kcj_cnt4)[wave] = sdfr_kcj_count(kcj_w[0], kcj_w[1], kcj_w[2], kcj_w[3]);
     };
     const bool kcj_top = kcj_on && P.n_mfma >= 2;       // the top operand (of the last hidden layer's product) is compacted: its masks are
@@ -1786,6 +1797,20 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
                 off = __builtin_amdgcn_readfirstlane(off);
                 tot = __builtin_amdgcn_readfirstlane(tot);
                 const uint32_t mine = lg == 0 ? kcj_w[0] : lg == 1 ? kcj_w[1] : lg == 2 ? kcj_w[2] : kcj_w[3];
+                if (kcj_fast) {
+                    // the place of register q: the set bits of the chain words in front of word q / 8 (wave-uniform, three sums) and one masked
+                    // population count of that word per lane -- no scalar chain in front of the stores (kcjd_slots.h)
+                    int cfront[4];
+                    cfront[0] = off;
+#pragma unroll
+                    for (int j = 1; j < 4; ++j) cfront[j] = cfront[j - 1] + sdfr_kcj_popc(kcj_c[j - 1]);
+                    const int dead = sdfr_kcjd_dead_pos(tot);       // (a dead register holds +0: stored where +0 or nothing is expected, no predicate)
+#pragma unroll
+                    for (int q = 0; q < 32; ++q) {
+                        const int pos = ((mine >> q) & 1u) ? sdfr_kcjd_rank_in_word(kcj_c[q >> 3], cfront[q >> 3], q, lg) : dead;
+                        act_e[sdfr_kcj_elem(pos, lp)] = acc[q >> 2][0][q & 3];
+                    }
+                } else {
                 int n = off;
 #pragma unroll
                 for (int q = 0; q < 32; ++q) {
@@ -1794,6 +1819,7 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
                     const int front = ((b0 << 2) | ((b0 + b1) << 4) | ((b0 + b1 + b2) << 6)) >> (2 * lg) & 3;      // survivors of q in the lane groups in front
                     if ((mine >> q) & 1u) act_e[sdfr_kcj_elem(n + front, lp)] = acc[q >> 2][0][q & 3];
                     n += b0 + b1 + b2 + b3;
+                }
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {           // k list: lane (lg, lp) enters the features of registers lp and lp + 16 of its lane group
