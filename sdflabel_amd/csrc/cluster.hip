@@ -2,8 +2,8 @@
 // cluster.  The reference has no counterpart to this stage; the semantics are this library's own (include/sdfr.h) and are
 // pinned by the numpy restatement tests/_cluster_ref.py.
 //
-// sdfr_lidar_clusters  participation -> the hash grid of normals.hip (counting sort: count, scan, scatter; no host sizing, no
-//                      synchronisation) -> one wave per sorted slot streams the 27 neighbouring cells' buckets 64 candidates at a time and
+// sdfr_lidar_clusters  participation, fused with the key pass of the hash grid (hash_grid.h, shared with normals.hip: counting sort; no host
+//                      sizing, no synchronisation) -> one wave per sorted slot streams the 27 neighbouring cells' buckets 64 candidates at a time and
 //                      unites the point with every neighbour of a lower index (union-find with parent[i] <= i, cluster_cells.h) -> flatten:
 //                      root and component size per point -> cluster flags, an exclusive scan in index order (= ascending smallest member),
 //                      labels -> offsets -> the stable partition into member lists (per-chunk counts, a scan over chunks per cluster, ranks
@@ -12,18 +12,10 @@
 // The order of a bucket's points depends on the scatter's integer atomics and the order of the unions on the schedule; neither reaches an
 // output: the root of a component is its smallest index whatever the order (cluster_cells.h), and everything after the flatten pass is a
 // function of the roots.  No float atomic, no sum of floats.  Compiled with -ffp-contract=off.
-#include "sdfr_common.h"
 #include "cluster_cells.h"
 
-#define CLU_SCAN_TPB 1024
-
 struct CluWs {
-    double* spts;                    // [N][3] the participating points in bucket order
-    uint64_t* skey;                  // [N]    their cell keys
-    uint64_t* pkey;                  // [N]    cell key per input point, ~0 for a point that takes no part
-    int32_t* start;                  // [T + 1] first slot of every bucket; start[T] = the number of participating points
-    int32_t* count;                  // [T]
-    int32_t* sidx;                   // [N]    input index of every slot
+    HashGrid grid;                   // of the participating points
     int32_t* parent;                 // [N]
     int32_t* root;                   // [N]    -1 for a point that takes no part
     int32_t* csize;                  // [N]    component size, at the root
@@ -36,18 +28,14 @@ struct CluWs {
 static int64_t clu_chunks(int64_t N) { return (N + CLU_CHUNK - 1) / CLU_CHUNK; }
 
 static int64_t clu_carve(void* base, int64_t N, int64_t C, CluWs* ws) {
-    const int64_t T = clu_table(N);
     char* p = (char*)base;
     int64_t at = 0;
     auto take = [&](int64_t bytes) { char* q = p ? p + at : nullptr; at += (bytes + 15) / 16 * 16; return q; };
-    char* a = take(N * 24); char* b = take(N * 8); char* c = take(N * 8); char* d = take((T + 1) * 4); char* e = take(T * 4);
-    char* f = take(N * 4); char* g = take(N * 4); char* h = take(N * 4); char* i = take(N * 4); char* j = take(N * 4);
-    char* k = take((N + 1) * 4); char* l = take(C * 4); char* m = take(clu_chunks(N) * C * 4);
-    if (ws) {
-        ws->spts = (double*)a; ws->skey = (uint64_t*)b; ws->pkey = (uint64_t*)c; ws->start = (int32_t*)d; ws->count = (int32_t*)e;
-        ws->sidx = (int32_t*)f; ws->parent = (int32_t*)g; ws->root = (int32_t*)h; ws->csize = (int32_t*)i; ws->isc = (int32_t*)j;
-        ws->cid = (int32_t*)k; ws->csz = (int32_t*)l; ws->hist = (int32_t*)m;
-    }
+    CluWs w;
+    w.grid = hg_carve(N, take);
+    w.parent = (int32_t*)take(N * 4); w.root = (int32_t*)take(N * 4); w.csize = (int32_t*)take(N * 4); w.isc = (int32_t*)take(N * 4);
+    w.cid = (int32_t*)take((N + 1) * 4); w.csz = (int32_t*)take(C * 4); w.hist = (int32_t*)take(clu_chunks(N) * C * 4);
+    if (ws) *ws = w;
     return at;
 }
 
@@ -74,73 +62,8 @@ __global__ __launch_bounds__(256) void sdfr_clu_key_kernel(const T* __restrict__
     const int part = clu_takes_part(mask ? mask[i] != 0 : 1, X, Y, Z);
     parent[i] = i;
     csize[i] = 0;
-    if (part == 1) {
-        const uint64_t key = clu_pack(clu_cell(X, cell), clu_cell(Y, cell), clu_cell(Z, cell));
-        pkey[i] = key;
-        atomicAdd(&count[clu_bucket(key, shift)], 1);
-    } else {
-        pkey[i] = ~0ull;
-        if (part == 2) atomicOr(&counts[3], CLU_FLAG_NONFINITE);
-    }
-}
-
-// Exclusive scan of in[n] into out[n + 1] by one workgroup, 4096 elements per round; in and out may not overlap.
-__global__ __launch_bounds__(CLU_SCAN_TPB) void sdfr_clu_scan_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out, int64_t n) {
-    __shared__ int wsum[CLU_SCAN_TPB / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int carry = 0;
-    for (int64_t base = 0; base < n; base += 4 * CLU_SCAN_TPB) {
-        const int64_t e = base + 4 * t;
-        int c[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) c[k] = e + k < n ? in[e + k] : 0;
-        const int s = (c[0] + c[1]) + (c[2] + c[3]);
-        int v = s;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int m = __shfl_up(v, o);
-            if (lane >= o) v += m;
-        }
-        if (lane == 63) wsum[wave] = v;
-        __syncthreads();
-        int woff = 0, tot = 0;
-#pragma unroll
-        for (int k = 0; k < CLU_SCAN_TPB / 64; ++k) {
-            const int x = wsum[k];
-            if (k < wave) woff += x;
-            tot += x;
-        }
-        int ex = carry + woff + v - s;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (e + k < n) out[e + k] = ex;
-            ex += c[k];
-        }
-        carry += tot;
-        __syncthreads();
-    }
-    if (t == 0) out[n] = carry;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void sdfr_clu_scatter_kernel(const T* __restrict__ pts, int N, const uint64_t* __restrict__ pkey, int shift,
-                                                              const int32_t* __restrict__ start, int32_t* __restrict__ count,
-                                                              int32_t* __restrict__ sidx, uint64_t* __restrict__ skey, double* __restrict__ spts) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const uint64_t key = pkey[i];
-    if (key == ~0ull) return;
-    const int b = clu_bucket(key, shift);
-    const int pos = start[b] + atomicAdd(&count[b], 1);                  // < start[b + 1] <= N: the counts are those of the key pass
-    sidx[pos] = i;
-    skey[pos] = key;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) spts[3 * (int64_t)pos + k] = (double)pts[3 * (int64_t)i + k];
-}
-
-__global__ __launch_bounds__(256) void sdfr_clu_zero_kernel(int32_t* __restrict__ count, int64_t T) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < T) count[i] = 0;
+    hg_key_point(part == 1, X, Y, Z, cell, shift, i, pkey, count);
+    if (part == 2) atomicOr(&counts[3], CLU_FLAG_NONFINITE);
 }
 
 // One wave per slot of the sorted cloud: unite the slot's point i with every neighbour j < i (every edge is seen from its larger end).
@@ -151,41 +74,21 @@ __global__ __launch_bounds__(256) void sdfr_clu_zero_kernel(int32_t* __restrict_
 __global__ __launch_bounds__(64) void sdfr_clu_union_kernel(const int32_t* __restrict__ start, int64_t T, int shift, const int32_t* __restrict__ sidx,
                                                            const uint64_t* __restrict__ skey, const double* __restrict__ spts, double e2,
                                                            int32_t* parent) {
-    __shared__ uint64_t ck[27];
-    __shared__ int cs[27], cpre[28];
+    __shared__ HgWalk cells;
     const int w = blockIdx.x, lane = threadIdx.x;
     if (w >= start[T]) return;                                           // (the same for the whole wave)
     const int i = sidx[w];
     const double q[3] = {spts[3 * (int64_t)w], spts[3 * (int64_t)w + 1], spts[3 * (int64_t)w + 2]};
-    const uint64_t qkey = skey[w];
-    if (lane < 27) {
-        int s = 0, len = 0;
-        uint64_t k = 0;
-        if (clu_neighbour_cell(qkey, lane, &k)) {
-            const int b = clu_bucket(k, shift);
-            s = start[b];
-            len = start[b + 1] - s;
-        }
-        cs[lane] = s; ck[lane] = k; cpre[lane + 1] = len;
-    }
-    __syncthreads();
-    if (lane == 0) {
-        cpre[0] = 0;
-        for (int k = 1; k <= 27; ++k) cpre[k] += cpre[k - 1];
-    }
-    __syncthreads();
-    const int M = cpre[27];
+    const int M = hg_walk_cells(cells, skey[w], start, shift, lane);
     for (int base = 0; base < M; base += 64) {
         const int c = base + lane;
         if (c >= M) continue;
-        int s = 0;
-        for (int k = 1; k < 27; ++k) s += cpre[k] <= c ? 1 : 0;          // the cell whose range holds candidate c
-        const int pos = cs[s] + (c - cpre[s]);
-        if (skey[pos] != ck[s]) continue;                                // another cell of the same bucket: not this cell's point
+        int pos;
+        if (!hg_walk_slot(cells, skey, c, &pos)) continue;
         const int j = sidx[pos];
         if (j >= i) continue;
         const double p[3] = {spts[3 * (int64_t)pos], spts[3 * (int64_t)pos + 1], spts[3 * (int64_t)pos + 2]};
-        if (clu_near(p, q, e2)) clu_union(parent, i, j);
+        if (hg_d2(p, q) < e2) clu_union(parent, i, j);
     }
 }
 
@@ -381,46 +284,36 @@ extern "C" int sdfr_lidar_clusters(const void* points, int points_f64, int N, co
     SDFR_REQUIRE(((uintptr_t)workspace & 15) == 0, "sdfr_lidar_clusters: the workspace must be 16-byte aligned");
     CluWs ws;
     SDFR_REQUIRE(workspace_bytes >= clu_carve(workspace, N, max_clusters, &ws), "sdfr_lidar_clusters: workspace too small (sdfr_cluster_ws_bytes)");
+    HashGrid& g = ws.grid;
+    g.cell = hg_cell_width(eps);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t T = clu_table(N);
-    const int shift = 64 - clu_log2(T);
     const int C = max_clusters, chunks = (int)clu_chunks(N);
-    const double cell = clu_cell_width(eps);
-    const int64_t ninit = T > C ? T : C;
-    hipLaunchKernelGGL(sdfr_clu_init_kernel, dim3(sdfr_cdiv(ninit, 256)), dim3(256), 0, s, ws.count, T, ws.csz, C, counts);
+    const int64_t ninit = g.T > C ? g.T : C;
+    hipLaunchKernelGGL(sdfr_clu_init_kernel, dim3(sdfr_cdiv(ninit, 256)), dim3(256), 0, s, g.count, g.T, ws.csz, C, counts);
     SDFR_LAUNCH_CHECK();
     if (N > 0) {
         const dim3 per_point(sdfr_cdiv(N, 256));
         if (points_f64)
-            hipLaunchKernelGGL(sdfr_clu_key_kernel<double>, per_point, dim3(256), 0, s, (const double*)points, mask, N, cell, shift, ws.pkey, ws.count,
+            hipLaunchKernelGGL(sdfr_clu_key_kernel<double>, per_point, dim3(256), 0, s, (const double*)points, mask, N, g.cell, g.shift, g.pkey, g.count,
                                ws.parent, ws.csize, counts);
         else
-            hipLaunchKernelGGL(sdfr_clu_key_kernel<float>, per_point, dim3(256), 0, s, (const float*)points, mask, N, cell, shift, ws.pkey, ws.count,
+            hipLaunchKernelGGL(sdfr_clu_key_kernel<float>, per_point, dim3(256), 0, s, (const float*)points, mask, N, g.cell, g.shift, g.pkey, g.count,
                                ws.parent, ws.csize, counts);
         SDFR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sdfr_clu_scan_kernel, dim3(1), dim3(CLU_SCAN_TPB), 0, s, ws.count, ws.start, T);
+        const int sorted = hg_sort(g, points, points_f64, N, s);
+        if (sorted != SDFR_OK) return sorted;
+        hipLaunchKernelGGL(sdfr_clu_union_kernel, dim3(N), dim3(64), 0, s, g.start, g.T, g.shift, g.sidx, g.skey, g.spts, eps * eps, ws.parent);
         SDFR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sdfr_clu_zero_kernel, dim3(sdfr_cdiv(T, 256)), dim3(256), 0, s, ws.count, T);
-        SDFR_LAUNCH_CHECK();
-        if (points_f64)
-            hipLaunchKernelGGL(sdfr_clu_scatter_kernel<double>, per_point, dim3(256), 0, s, (const double*)points, N, ws.pkey, shift, ws.start, ws.count,
-                               ws.sidx, ws.skey, ws.spts);
-        else
-            hipLaunchKernelGGL(sdfr_clu_scatter_kernel<float>, per_point, dim3(256), 0, s, (const float*)points, N, ws.pkey, shift, ws.start, ws.count,
-                               ws.sidx, ws.skey, ws.spts);
-        SDFR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sdfr_clu_union_kernel, dim3(N), dim3(64), 0, s, ws.start, T, shift, ws.sidx, ws.skey, ws.spts, eps * eps, ws.parent);
-        SDFR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sdfr_clu_flatten_kernel, per_point, dim3(256), 0, s, N, ws.pkey, ws.parent, ws.root, ws.csize, counts);
+        hipLaunchKernelGGL(sdfr_clu_flatten_kernel, per_point, dim3(256), 0, s, N, g.pkey, ws.parent, ws.root, ws.csize, counts);
         SDFR_LAUNCH_CHECK();
         hipLaunchKernelGGL(sdfr_clu_mark_kernel, per_point, dim3(256), 0, s, N, ws.root, ws.csize, min_points, max_points, ws.isc);
         SDFR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sdfr_clu_scan_kernel, dim3(1), dim3(CLU_SCAN_TPB), 0, s, ws.isc, ws.cid, (int64_t)N);
+        hipLaunchKernelGGL(sdfr_hg_scan_kernel<false>, dim3(1), dim3(HG_SCAN_TPB), 0, s, ws.isc, ws.cid, (int64_t)N);
         SDFR_LAUNCH_CHECK();
         hipLaunchKernelGGL(sdfr_clu_label_kernel, per_point, dim3(256), 0, s, N, ws.root, ws.csize, ws.isc, ws.cid, C, label, ws.csz, counts);
         SDFR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(sdfr_clu_scan_kernel, dim3(1), dim3(CLU_SCAN_TPB), 0, s, ws.csz, off, (int64_t)C);
+    hipLaunchKernelGGL(sdfr_hg_scan_kernel<false>, dim3(1), dim3(HG_SCAN_TPB), 0, s, ws.csz, off, (int64_t)C);
     SDFR_LAUNCH_CHECK();
     if (N > 0) {
         hipLaunchKernelGGL(sdfr_clu_hist_kernel, dim3(chunks), dim3(CLU_CHUNK), 0, s, N, label, C, ws.hist);

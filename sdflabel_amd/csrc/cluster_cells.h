@@ -2,12 +2,9 @@
 // Everything here is a plain function of one point, one pair, one component or one (point, direction), compiled for the device by cluster.hip
 // and for the host by tests/cluster_host/cluster_host.cpp, which runs the threads as loops and is compared with the numpy restatement
 // (tests/_cluster_ref.py) bit for bit.  Both translation units are compiled with -ffp-contract=off: every operation rounds separately.
-// The hash grid is that of normals.hip (cells a little wider than the radius, 21 bits per axis, a multiplicative hash into a power-of-two
-// table); it is restated here and not shared, because normals.hip's key pass is fused with its frustum test and default outputs and because
-// the host program needs the cell functions as host code.
+// The hash grid and the distance rule are hash_grid.h's (hg_*), shared with normals.hip and compiled for the host through this header.
 #pragma once
-#include <math.h>
-#include <stdint.h>
+#include "hash_grid.h"
 
 #if defined(__HIPCC__)
 #define CLU_HD __host__ __device__ inline
@@ -15,7 +12,6 @@
 #define CLU_HD static inline
 #endif
 
-#define CLU_HALF (1 << 20)              // cell coordinates are clamped to [-2^20, 2^20) and stored with this offset: 21 bits per axis
 #define CLU_CHUNK 1024                  // points per chunk of the stable partition
 #define CLU_MAX_POINTS (1 << 24)
 #define CLU_MAX_CLUSTERS 4096           // one LDS counter per kept cluster
@@ -33,46 +29,6 @@ CLU_HD bool clu_finite(double a) { return fabs(a) <= 1.7976931348623157e308; }  
 CLU_HD int clu_takes_part(int masked_in, double x, double y, double z) {
     if (!masked_in) return 0;
     return clu_finite(x) && clu_finite(y) && clu_finite(z) ? 1 : 2;
-}
-
-CLU_HD double clu_cell_width(double eps) { return eps * (1.0 + 1.0 / 1048576.0); }              // a little wider than eps: rounding of p / cell
-                                                                                                // cannot put a neighbour two cells away
-CLU_HD int clu_cell(double p, double cell) {
-    double c = floor(p / cell);
-    if (!(c >= (double)-CLU_HALF)) c = (double)-CLU_HALF;
-    if (c > (double)(CLU_HALF - 1)) c = (double)(CLU_HALF - 1);
-    return (int)c + CLU_HALF;
-}
-
-CLU_HD uint64_t clu_pack(int cx, int cy, int cz) { return ((uint64_t)cx << 42) | ((uint64_t)cy << 21) | (uint64_t)cz; }
-
-CLU_HD int clu_bucket(uint64_t key, int shift) { return (int)((key * 0x9E3779B97F4A7C15ull) >> shift); }
-
-CLU_HD int64_t clu_table(int64_t N) {                                    // buckets of the hash grid: a power of two, at least 2 N
-    int64_t T = 64;
-    while (T < 2 * N) T <<= 1;
-    return T;
-}
-
-CLU_HD int clu_log2(int64_t T) {
-    int l = 0;
-    while (((int64_t)1 << l) < T) ++l;
-    return l;
-}
-
-// key of the k-th (0 ... 26) neighbouring cell of the cell `key`; false where it leaves the 21-bit range
-CLU_HD bool clu_neighbour_cell(uint64_t key, int k, uint64_t* out) {
-    const int nx = (int)((key >> 42) & 0x1FFFFF) + k % 3 - 1, ny = (int)((key >> 21) & 0x1FFFFF) + (k / 3) % 3 - 1, nz = (int)(key & 0x1FFFFF) + k / 9 - 1;
-    if (!(nx >= 0 && nx < 2 * CLU_HALF && ny >= 0 && ny < 2 * CLU_HALF && nz >= 0 && nz < 2 * CLU_HALF)) return false;
-    *out = clu_pack(nx, ny, nz);
-    return true;
-}
-
-// neighbours: d2 = (dx*dx + dy*dy) + dz*dz < eps*eps, strictly, in float64 (sdfr_lidar_normals' rule)
-CLU_HD bool clu_near(const double* a, const double* b, double e2) {
-    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-    const double d2 = (dx * dx + dy * dy) + dz * dz;
-    return d2 < e2;
 }
 
 // ---- union-find over input indices ------------------------------------------------------------------------------------------------------

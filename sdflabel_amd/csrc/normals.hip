@@ -1,18 +1,17 @@
 // Lidar normals on the device (gfx950): the road-plane removal of the reference's get_kitti_frame (utils/refinement.py:612-656), i.e. Open3D's
 // estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) restated as our own semantics (include/sdfr.h; parity with Open3D is NOT tested).
 //
-// sdfr_lidar_normals   frustum test -> a hash grid of cells a little wider than the radius, built by a counting sort (count, scan, scatter: no
-//                      host sizing, no synchronisation) -> one wave per frustum point: the 27 neighbouring cells' buckets are streamed 64
-//                      candidates at a time and the running best max_nn by (d2, index) is kept across the lanes by rank counting -> mean,
-//                      centred covariance and the Jacobi eigenvector in lane 0, in neighbour order.
+// sdfr_lidar_normals   frustum test, fused with the key pass of the hash grid (hash_grid.h, shared with cluster.hip: cells a little wider
+//                      than the radius, sorted by scan and scatter) -> one wave per frustum point: the 27 neighbouring cells' buckets are
+//                      streamed 64 candidates at a time (the cells and the slot of a candidate are hash_grid.h's) and the running best max_nn
+//                      by (d2, index) is kept across the lanes by rank counting -> mean, centred covariance and the Jacobi eigenvector in
+//                      lane 0, in neighbour order.
 // The order of a bucket's points depends on the scatter's integer atomics; the selection does not depend on the order candidates arrive in
 // (ranks of a strict total order), so the results are the same bits on every run.  No float atomic.
-// Compiled with -ffp-contract=off: d2 = (dx*dx + dy*dy) + dz*dz rounds as written.
-#include "sdfr_common.h"
+// Compiled with -ffp-contract=off: hg_d2's d2 = (dx*dx + dy*dy) + dz*dz rounds as written.
+#include "hash_grid.h"
 #include "jacobi3.h"
 
-#define NRM_HALF (1 << 20)           // cell coordinates are clamped to [-2^20, 2^20) and stored with this offset: 21 bits per axis
-#define NRM_SCAN_TPB 1024
 #define NRM_MAX_POINTS (1 << 28)
 
 struct NrmPlanes {
@@ -20,47 +19,14 @@ struct NrmPlanes {
     int use;
 };
 
-static int64_t nrm_table(int64_t N) {                                   // buckets of the hash grid: a power of two, at least 2 N
-    int64_t T = 64;
-    while (T < 2 * N) T <<= 1;
-    return T;
-}
-
-static int nrm_log2(int64_t T) {
-    int l = 0;
-    while (((int64_t)1 << l) < T) ++l;
-    return l;
-}
-
-struct NrmWs {
-    double* spts;                    // [N][3] the frustum points in bucket order
-    uint64_t* skey;                  // [N]    their cell keys
-    uint64_t* pkey;                  // [N]    cell key per input point, ~0 outside the frustum
-    int32_t* start;                  // [T + 4] first slot of every bucket; start[T] = the number of frustum points
-    int32_t* count;                  // [T]
-    int32_t* sidx;                   // [N]    input index of every slot
-};
-
-static int64_t nrm_carve(void* base, int64_t N, NrmWs* ws) {
-    const int64_t T = nrm_table(N);
+// the workspace is the grid and nothing else: its taking points are the frustum points
+static int64_t nrm_carve(void* base, int64_t N, HashGrid* ws) {
     char* p = (char*)base;
     int64_t at = 0;
-    auto take = [&](int64_t bytes) { char* q = p ? p + at : nullptr; at += (bytes + 15) / 16 * 16; return q; };
-    char* a = take(N * 24); char* b = take(N * 8); char* c = take(N * 8); char* d = take((T + 4) * 4); char* e = take(T * 4); char* f = take(N * 4);
-    if (ws) { ws->spts = (double*)a; ws->skey = (uint64_t*)b; ws->pkey = (uint64_t*)c; ws->start = (int32_t*)d; ws->count = (int32_t*)e; ws->sidx = (int32_t*)f; }
+    const HashGrid g = hg_carve(N, [&](int64_t bytes) { char* q = p ? p + at : nullptr; at += (bytes + 15) / 16 * 16; return q; });
+    if (ws) *ws = g;
     return at;
 }
-
-__device__ __forceinline__ int nrm_cell(double p, double cell) {
-    double c = floor(p / cell);
-    if (!(c >= (double)-NRM_HALF)) c = (double)-NRM_HALF;               // (a NaN lands here too)
-    if (c > (double)(NRM_HALF - 1)) c = (double)(NRM_HALF - 1);
-    return (int)c + NRM_HALF;
-}
-
-__device__ __forceinline__ uint64_t nrm_pack(int cx, int cy, int cz) { return ((uint64_t)cx << 42) | ((uint64_t)cy << 21) | (uint64_t)cz; }
-
-__device__ __forceinline__ int nrm_bucket(uint64_t key, int shift) { return (int)((key * 0x9E3779B97F4A7C15ull) >> shift); }
 
 __global__ __launch_bounds__(256) void sdfr_nrm_init_kernel(int32_t* __restrict__ count, int64_t T) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -83,69 +49,13 @@ __global__ __launch_bounds__(256) void sdfr_nrm_key_kernel(const T* __restrict__
             in = in && (((double)fr.pl[3 * k] * X + (double)fr.pl[3 * k + 1] * Y) + (double)fr.pl[3 * k + 2] * Z > 0.0);
     }
     in_frustum[i] = in ? 1 : 0;
-    if (in) {
-        const uint64_t key = nrm_pack(nrm_cell(X, cell), nrm_cell(Y, cell), nrm_cell(Z, cell));
-        pkey[i] = key;
-        atomicAdd(&count[nrm_bucket(key, shift)], 1);
-    } else {
-        pkey[i] = ~0ull;
+    hg_key_point(in, X, Y, Z, cell, shift, i, pkey, count);
+    if (!in) {
         normals[3 * (int64_t)i] = 0.0; normals[3 * (int64_t)i + 1] = 0.0; normals[3 * (int64_t)i + 2] = 1.0;
         nn_count[i] = 0;
         if (nn_idx)
             for (int k = 0; k < max_nn; ++k) nn_idx[(int64_t)i * max_nn + k] = -1;
     }
-}
-
-// Exclusive scan of count[T] into start[T + 1] by one workgroup, 4096 buckets per round; count is zeroed for the scatter.
-__global__ __launch_bounds__(NRM_SCAN_TPB) void sdfr_nrm_scan_kernel(int32_t* __restrict__ count, int32_t* __restrict__ start, int64_t T) {
-    __shared__ int wsum[NRM_SCAN_TPB / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int carry = 0;
-    for (int64_t base = 0; base < T; base += 4 * NRM_SCAN_TPB) {
-        const int64_t e = base + 4 * t;                                  // T is a multiple of 4: e < T covers e + 3
-        int4 c = make_int4(0, 0, 0, 0);
-        if (e < T) c = *(const int4*)(count + e);
-        const int s = c.x + c.y + c.z + c.w;
-        int v = s;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int n = __shfl_up(v, o);
-            if (lane >= o) v += n;
-        }
-        if (lane == 63) wsum[wave] = v;
-        __syncthreads();
-        int woff = 0, tot = 0;
-#pragma unroll
-        for (int k = 0; k < NRM_SCAN_TPB / 64; ++k) {
-            const int x = wsum[k];
-            if (k < wave) woff += x;
-            tot += x;
-        }
-        const int ex = carry + woff + v - s;
-        if (e < T) {
-            *(int4*)(start + e) = make_int4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
-            *(int4*)(count + e) = make_int4(0, 0, 0, 0);
-        }
-        carry += tot;
-        __syncthreads();
-    }
-    if (t == 0) start[T] = carry;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void sdfr_nrm_scatter_kernel(const T* __restrict__ pts, int N, const uint64_t* __restrict__ pkey, int shift,
-                                                              const int32_t* __restrict__ start, int32_t* __restrict__ count,
-                                                              int32_t* __restrict__ sidx, uint64_t* __restrict__ skey, double* __restrict__ spts) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const uint64_t key = pkey[i];
-    if (key == ~0ull) return;
-    const int b = nrm_bucket(key, shift);
-    const int pos = start[b] + atomicAdd(&count[b], 1);                  // < start[b + 1] <= N: the counts are those of the key pass
-    sidx[pos] = i;
-    skey[pos] = key;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) spts[3 * (int64_t)pos + k] = (double)pts[3 * (int64_t)i + k];
 }
 
 __device__ __forceinline__ bool nrm_less(double da, int ja, double db, int jb) { return da < db || (da == db && ja < jb); }
@@ -159,33 +69,13 @@ __global__ __launch_bounds__(64) void sdfr_nrm_query_kernel(const int32_t* __res
                                                            double* __restrict__ normals, int32_t* __restrict__ nn_count,
                                                            int32_t* __restrict__ nn_idx) {
     __shared__ double bd[64], cd[64], px[64], py[64], pz[64];
-    __shared__ uint64_t ck[27];
-    __shared__ int bj[64], bp[64], cj[64], cp[64], cs[27], cpre[28];
+    __shared__ int bj[64], bp[64], cj[64], cp[64];
+    __shared__ HgWalk cells;
     const int w = blockIdx.x, lane = threadIdx.x;
     if (w >= start[T]) return;                                           // (the same for the whole wave)
     const int i = sidx[w];
-    const double qx = spts[3 * (int64_t)w], qy = spts[3 * (int64_t)w + 1], qz = spts[3 * (int64_t)w + 2];
-    const uint64_t qkey = skey[w];
-    if (lane < 27) {
-        const int nx = (int)((qkey >> 42) & 0x1FFFFF) + lane % 3 - 1, ny = (int)((qkey >> 21) & 0x1FFFFF) + (lane / 3) % 3 - 1,
-                  nz = (int)(qkey & 0x1FFFFF) + lane / 9 - 1;
-        int s = 0, len = 0;
-        uint64_t k = 0;
-        if (nx >= 0 && nx < 2 * NRM_HALF && ny >= 0 && ny < 2 * NRM_HALF && nz >= 0 && nz < 2 * NRM_HALF) {
-            k = nrm_pack(nx, ny, nz);
-            const int b = nrm_bucket(k, shift);
-            s = start[b];
-            len = start[b + 1] - s;
-        }
-        cs[lane] = s; ck[lane] = k; cpre[lane + 1] = len;
-    }
-    __syncthreads();
-    if (lane == 0) {
-        cpre[0] = 0;
-        for (int k = 1; k <= 27; ++k) cpre[k] += cpre[k - 1];
-    }
-    __syncthreads();
-    const int M = cpre[27];
+    const double q[3] = {spts[3 * (int64_t)w], spts[3 * (int64_t)w + 1], spts[3 * (int64_t)w + 2]};
+    const int M = hg_walk_cells(cells, skey[w], start, shift, lane);
     int nb = 0;
     double md = INFINITY;
     int mj = 0x7fffffff, mp = 0;
@@ -195,13 +85,10 @@ __global__ __launch_bounds__(64) void sdfr_nrm_query_kernel(const int32_t* __res
         double d = INFINITY;
         int j = 0x7fffffff, pos = 0;
         if (v) {
-            int s = 0;
-            for (int k = 1; k < 27; ++k) s += cpre[k] <= c ? 1 : 0;      // the cell whose range holds candidate c
-            pos = cs[s] + (c - cpre[s]);
-            v = skey[pos] == ck[s];                                      // another cell of the same bucket: not this cell's point
+            v = hg_walk_slot(cells, skey, c, &pos);
             if (v) {
-                const double dx = spts[3 * (int64_t)pos] - qx, dy = spts[3 * (int64_t)pos + 1] - qy, dz = spts[3 * (int64_t)pos + 2] - qz;
-                d = (dx * dx + dy * dy) + dz * dz;
+                const double p[3] = {spts[3 * (int64_t)pos], spts[3 * (int64_t)pos + 1], spts[3 * (int64_t)pos + 2]};
+                d = hg_d2(p, q);
                 j = sidx[pos];
                 v = d < r2;
             }
@@ -257,7 +144,7 @@ __global__ __launch_bounds__(64) void sdfr_nrm_query_kernel(const int32_t* __res
             const double len = sqrt((V[0][2] * V[0][2] + V[1][2] * V[1][2]) + V[2][2] * V[2][2]);
             if (len > 0.0 && len < INFINITY) {
                 for (int a = 0; a < 3; ++a) n[a] = V[a][2] / len;
-                if ((n[0] * qx + n[1] * qy) + n[2] * qz > 0.0)            // towards the camera; a product of exactly 0 keeps the solver's sign
+                if ((n[0] * q[0] + n[1] * q[1]) + n[2] * q[2] > 0.0)          // towards the camera; a product of exactly 0 keeps the solver's sign
                     for (int a = 0; a < 3; ++a) n[a] = -n[a];
             }
         }
@@ -280,34 +167,25 @@ extern "C" int sdfr_lidar_normals(const void* points, int points_f64, int N, con
     if (N == 0) return SDFR_OK;
     SDFR_REQUIRE(points && normals && nn_count && in_frustum && workspace, "sdfr_lidar_normals: NULL argument");
     SDFR_REQUIRE(((uintptr_t)workspace & 15) == 0, "sdfr_lidar_normals: the workspace must be 16-byte aligned");
-    NrmWs ws;
+    HashGrid ws;
     SDFR_REQUIRE(workspace_bytes >= nrm_carve(workspace, N, &ws), "sdfr_lidar_normals: workspace too small (sdfr_lidar_normals_ws_bytes)");
+    ws.cell = hg_cell_width(radius);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t T = nrm_table(N);
-    const int shift = 64 - nrm_log2(T);
-    const double cell = radius * (1.0 + 1.0 / 1048576.0);                // a little wider than the radius: rounding of p / cell cannot put a
-    NrmPlanes fr;                                                        // neighbour two cells away
+    NrmPlanes fr;
     fr.use = planes ? 1 : 0;
     for (int i = 0; i < 12; ++i) fr.pl[i] = planes ? planes[i] : 0.f;
-    hipLaunchKernelGGL(sdfr_nrm_init_kernel, dim3(sdfr_cdiv(T, 256)), dim3(256), 0, s, ws.count, T);
+    hipLaunchKernelGGL(sdfr_nrm_init_kernel, dim3(sdfr_cdiv(ws.T, 256)), dim3(256), 0, s, ws.count, ws.T);
     SDFR_LAUNCH_CHECK();
     if (points_f64)
-        hipLaunchKernelGGL(sdfr_nrm_key_kernel<double>, dim3(sdfr_cdiv(N, 256)), dim3(256), 0, s, (const double*)points, N, fr, cell, shift, ws.pkey,
-                           ws.count, in_frustum, normals, nn_count, nn_idx, max_nn);
+        hipLaunchKernelGGL(sdfr_nrm_key_kernel<double>, dim3(sdfr_cdiv(N, 256)), dim3(256), 0, s, (const double*)points, N, fr, ws.cell, ws.shift,
+                           ws.pkey, ws.count, in_frustum, normals, nn_count, nn_idx, max_nn);
     else
-        hipLaunchKernelGGL(sdfr_nrm_key_kernel<float>, dim3(sdfr_cdiv(N, 256)), dim3(256), 0, s, (const float*)points, N, fr, cell, shift, ws.pkey,
-                           ws.count, in_frustum, normals, nn_count, nn_idx, max_nn);
+        hipLaunchKernelGGL(sdfr_nrm_key_kernel<float>, dim3(sdfr_cdiv(N, 256)), dim3(256), 0, s, (const float*)points, N, fr, ws.cell, ws.shift,
+                           ws.pkey, ws.count, in_frustum, normals, nn_count, nn_idx, max_nn);
     SDFR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sdfr_nrm_scan_kernel, dim3(1), dim3(NRM_SCAN_TPB), 0, s, ws.count, ws.start, T);
-    SDFR_LAUNCH_CHECK();
-    if (points_f64)
-        hipLaunchKernelGGL(sdfr_nrm_scatter_kernel<double>, dim3(sdfr_cdiv(N, 256)), dim3(256), 0, s, (const double*)points, N, ws.pkey, shift,
-                           ws.start, ws.count, ws.sidx, ws.skey, ws.spts);
-    else
-        hipLaunchKernelGGL(sdfr_nrm_scatter_kernel<float>, dim3(sdfr_cdiv(N, 256)), dim3(256), 0, s, (const float*)points, N, ws.pkey, shift,
-                           ws.start, ws.count, ws.sidx, ws.skey, ws.spts);
-    SDFR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sdfr_nrm_query_kernel, dim3(N), dim3(64), 0, s, ws.start, T, shift, ws.sidx, ws.skey, ws.spts, radius * radius, max_nn,
+    const int sorted = hg_sort(ws, points, points_f64, N, s);
+    if (sorted != SDFR_OK) return sorted;
+    hipLaunchKernelGGL(sdfr_nrm_query_kernel, dim3(N), dim3(64), 0, s, ws.start, ws.T, ws.shift, ws.sidx, ws.skey, ws.spts, radius * radius, max_nn,
                        normals, nn_count, nn_idx);
     SDFR_LAUNCH_CHECK();
     return SDFR_OK;

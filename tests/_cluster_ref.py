@@ -145,7 +145,8 @@ def cluster_cases():
     rng = np.random.default_rng(11)
     out = {}
     centres = [[0, 0, 8], [3, 0.5, 9], [-4, 1, 12], [6, -1, 15], [0.2, 0, 20]]
-    for n in (0, 1, 2, 63, 64, 65, 1023, 1024, 1025, 2049):
+    # (4095 ... 8193: the scan over N runs 4096 elements per round, so these cross one and two rounds and carry between them)
+    for n in (0, 1, 2, 63, 64, 65, 1023, 1024, 1025, 2049, 4095, 4096, 4097, 8193):
         out["n%d" % n] = _case(_blobs(rng, n, centres), min_points=1 if n < 63 else 5)
     e = float(np.float32(EPS))
     out["exactly_eps_apart"] = _case([[0, 0, 8], [e, 0, 8]], f64=True, min_points=1)

@@ -1,5 +1,6 @@
-// Host harness of sdflabel_amd/csrc/cluster_cells.h: runs what the kernels of cluster.hip run, the threads as loops, and writes what they
-// would write.  tests/test_cluster_cpu.py compares the output with the numpy restatement (tests/_cluster_ref.py) bit for bit.
+// Host harness of sdflabel_amd/csrc/cluster_cells.h and, through it, of the cells part of hash_grid.h (the grid of normals.hip too): runs
+// what the kernels of cluster.hip run, the threads as loops, and writes what they would write.  tests/test_cluster_cpu.py compares the
+// output with the numpy restatement (tests/_cluster_ref.py) bit for bit; tests/test_normals_cpu.py runs the normals' radius through it.
 //   cluster_host IN OUT
 //   IN : int32 N, f64, has_mask, min_points, max_points, C, K, reverse; float32 eps; points [N][3] float32 or float64; uint8 mask[N] if
 //        has_mask; float64 dirs[K][2]
@@ -50,9 +51,9 @@ int main(int argc, char** argv) {
     if (!rd(f, dirs, 2 * (size_t)K)) return 3;
     fclose(f);
     auto coord = [&](int i, int k) { return f64 ? p64[3 * (size_t)i + k] : (double)p32[3 * (size_t)i + k]; };
-    const double eps = (double)eps32, e2 = eps * eps, cell = clu_cell_width(eps);
-    const int64_t T = clu_table(N);
-    const int shift = 64 - clu_log2(T);
+    const double eps = (double)eps32, e2 = eps * eps, cell = hg_cell_width(eps);
+    const int64_t T = hg_table(N);
+    const int shift = 64 - hg_log2(T);
     const int chunks = (N + CLU_CHUNK - 1) / CLU_CHUNK;
     std::vector<double> spts(3 * (size_t)N);
     std::vector<uint64_t> skey((size_t)N), pkey((size_t)N);
@@ -67,8 +68,8 @@ int main(int argc, char** argv) {
         parent[i] = i;
         csize[i] = 0;
         if (part == 1) {
-            pkey[i] = clu_pack(clu_cell(X, cell), clu_cell(Y, cell), clu_cell(Z, cell));
-            count[clu_bucket(pkey[i], shift)] += 1;
+            pkey[i] = hg_pack(hg_cell(X, cell), hg_cell(Y, cell), hg_cell(Z, cell));
+            count[hg_bucket(pkey[i], shift)] += 1;
         } else {
             pkey[i] = ~0ull;
             if (part == 2) counts[3] |= CLU_FLAG_NONFINITE;
@@ -80,7 +81,7 @@ int main(int argc, char** argv) {
     for (int n = 0; n < N; ++n) {
         const int i = reverse ? N - 1 - n : n;
         if (pkey[i] == ~0ull) continue;
-        const int b = clu_bucket(pkey[i], shift);
+        const int b = hg_bucket(pkey[i], shift);
         const int pos = start[b] + count[b]++;
         sidx[pos] = i;
         skey[pos] = pkey[i];
@@ -98,8 +99,8 @@ int main(int argc, char** argv) {
         for (int k = 0; k < 27; ++k) {
             int s = 0, len = 0;
             uint64_t key = 0;
-            if (clu_neighbour_cell(skey[w], k, &key)) {
-                const int b = clu_bucket(key, shift);
+            if (hg_neighbour_cell(skey[w], k, &key)) {
+                const int b = hg_bucket(key, shift);
                 s = start[b];
                 len = start[b + 1] - s;
             }
@@ -113,7 +114,7 @@ int main(int argc, char** argv) {
             if (skey[pos] != ck[s]) continue;
             const int j = sidx[pos];
             if (j >= i) continue;
-            if (clu_near(&spts[3 * (size_t)pos], q, e2)) clu_union(parent.data(), i, j);
+            if (hg_d2(&spts[3 * (size_t)pos], q) < e2) clu_union(parent.data(), i, j);
         }
     }
     // flatten, mark, number, label

@@ -226,6 +226,10 @@ def test_c_argument_checks_need_no_gpu():
     assert 0 < h.sdfr_cluster_ws_bytes(0, 16) < h.sdfr_cluster_ws_bytes(1000, 16) < h.sdfr_cluster_ws_bytes(120000, 16) < h.sdfr_cluster_ws_bytes(120000, 512)
     assert h.sdfr_cluster_ws_bytes(-1, 16) == -1 and h.sdfr_cluster_ws_bytes(10, 0) == -1 and h.sdfr_cluster_ws_bytes(10, 4097) == -1
     assert h.sdfr_cluster_ws_bytes((1 << 24) + 1, 16) == -1 and h.sdfr_cluster_ws_bytes(1 << 24, 4096) > 0 and h.sdfr_cluster_ws_bytes(1 << 24, 4096) % 16 == 0
+    # read from the library as it was before the grid's arrays were carved by hash_grid.h: callers' allocations must not change
+    before = {0: (608, 2592), 1: (816, 4784), 31: (2688, 6656), 32: (2720, 6688), 33: (3376, 7344), 1000: (80544, 84512), 120000: (9784800, 10020896)}
+    for n, want in before.items():
+        assert (h.sdfr_cluster_ws_bytes(n, 16), h.sdfr_cluster_ws_bytes(n, 512)) == want, n
     big = h.sdfr_cluster_ws_bytes(1000, 16)
     assert h.sdfr_lidar_clusters(d, 0, -1, None, 0.5, 10, 0, 16, d, d, d, d, d, big, None) == inv and b"point count" in h.sdfr_last_error()
     assert h.sdfr_lidar_clusters(d, 0, 1000, None, 0.5, 10, 0, 0, d, d, d, d, d, big, None) == inv and b"max_clusters" in h.sdfr_last_error()

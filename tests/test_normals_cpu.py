@@ -89,6 +89,10 @@ def test_new_entry_points_are_exported_declared_and_bound():
     # the workspace grows with N and is refused beyond the limit
     assert 0 < h.sdfr_lidar_normals_ws_bytes(0) < h.sdfr_lidar_normals_ws_bytes(1000) < h.sdfr_lidar_normals_ws_bytes(120000)
     assert h.sdfr_lidar_normals_ws_bytes(-1) == -1
+    # read from the library as it was before the grid's arrays were carved by hash_grid.h: callers' allocations must not change
+    before = {0: 528, 1: 608, 31: 1920, 32: 1936, 33: 2528, 1000: 60400, 120000: 7377168}
+    for n, want in before.items():
+        assert h.sdfr_lidar_normals_ws_bytes(n) == want, n
     # argument validation happens before any HIP call
     assert h.sdfr_lidar_normals(None, 1, 10, None, 1.0, 30, None, None, None, None, None, 0, None) == -1 and b"NULL" in h.sdfr_last_error()
     assert h.sdfr_lidar_normals(None, 1, 10, None, 1.0, 65, None, None, None, None, None, 0, None) == -1 and b"max_nn" in h.sdfr_last_error()
@@ -96,6 +100,32 @@ def test_new_entry_points_are_exported_declared_and_bound():
     assert h.sdfr_lidar_normals(None, 1, -1, None, 1.0, 30, None, None, None, None, None, 0, None) == -1
     assert h.sdfr_lidar_normals(None, 1, 0, None, 1.0, 30, None, None, None, None, None, 0, None) == 0
     assert h.sdfr_depth_map_masked(None, 1, 10, None, None, None, 8, 8, None, None, None, None) == -1 and b"NULL" in h.sdfr_last_error()
+
+
+def test_grid_rules_on_the_host_find_the_radius_graphs_components(tmp_path):
+    """csrc/hash_grid.h is one header for the normals and the clusters, and tests/cluster_host is its host build.  Run with eps = the
+    normals' radius and the frustum as the mask, the harness walks the normals' grid (cell width from the radius, clamp, 27 cells, bucket
+    collisions) over the normals' points; its components must be those of the radius graph, which scipy finds without any grid."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    from scipy.spatial import cKDTree
+    from tests import _cluster_ref as CR
+    from tests._util import build_host_program
+    from tests.test_cluster_cpu import _near_threshold, _run_host
+    radius = 1.0
+    P = np.ascontiguousarray(NR.street(1)[:900], np.float32)
+    inside = NR.in_frustum(P, NR.KITTI_K, *NR.KITTI_WH)
+    idx = np.nonzero(inside)[0]
+    assert 100 < len(idx) < len(P) and not _near_threshold(P, inside, radius)     # scipy keeps d <= radius, the rule is strict: no pair is at it
+    case = {"points": P, "mask": inside.astype(np.uint8), "kw": dict(eps=radius, min_points=1, max_points=None, max_clusters=1024)}
+    exe = build_host_program(tmp_path, "cluster_host/cluster_host.cpp", "cluster_host")
+    label, _, _, counts, _ = _run_host(exe, tmp_path, case, CR.directions(1), 0)
+    pr = cKDTree(P[idx].astype(np.float64)).query_pairs(radius, output_type="ndarray")
+    ncomp, lab = connected_components(coo_matrix((np.ones(len(pr)), (pr[:, 0], pr[:, 1])), shape=(len(idx), len(idx))), directed=False)
+    assert 1 < ncomp < len(idx) and counts.tolist() == [len(idx), ncomp, ncomp, 0]
+    assert (label[~inside] == -1).all() and (label[idx] >= 0).all()
+    # the same partition: one scipy label per component number and one component number per scipy label
+    assert len(set(zip(lab.tolist(), label[idx].tolist()))) == ncomp
 
 
 def test_no_cpu_fallback(monkeypatch):
