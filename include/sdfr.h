@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 422        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 423        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -51,7 +51,8 @@ extern "C" {
  * frozen decoder, sdfr_encode_*; 419: shape completion from one view, sdfr_view_samples and
  * sdfr_bound_*; 420: pose and shape fitted to one view, sdfr_align_*;
  * 421: lidar clusters and rough boxes, sdfr_cluster_* and sdfr_lidar_clusters; 422: band selection and tile ranking in one launch,
- * sdfr_mlp_forward_balanced_deferred and sdfr_band_select_rank).  A caller built
+ * sdfr_mlp_forward_balanced_deferred and sdfr_band_select_rank;
+ * 423: one shape fitted to several views, sdfr_track_step).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -1314,6 +1315,44 @@ int sdfr_align_reduce(const float* pred, const float* lo, const float* hi, const
 int sdfr_align_step(float* z, float* m, float* v, int L, int B, int unit, float* theta, float* tm, float* tv, float* pose, const double* g,
                     const double* loss, int32_t* flags, float code_reg, float lr, const float* lr_pose, int t, float* history, int64_t history_stride,
                     void* stream);
+
+/* ---- one shape fitted to several views (csrc/track.hip, SDFR_VERSION 423) ----
+ *
+ * A VIEW is one cloud of one object in one camera frame, with its own yaw and trans; a TRACK is an object: an ordered list of views with ONE
+ * latent and (with share_scale) ONE scale.  Views are numbered 0 .. V - 1; track t owns views voff[t] .. voff[t + 1] - 1.  One iteration of
+ * the joint fit is  sdfr_align_rows over the V views with z = z_view [V][L] -> the decoder forward with its masks saved -> sdfr_mlp_jacobian
+ * -> sdfr_align_reduce over the V views (loss [V], g [V][L + 5], vflags [V]) -> sdfr_track_step.  The first four are unchanged.
+ *
+ * sdfr_track_step: ONE launch, grid (T), one workgroup a track.  All pointers are device pointers (but lr_pose, five floats of the host read
+ * before the launch); no atomics, no memset, no host synchronisation, the same bits on every run, and a track's results do not depend on T
+ * or on its position in the batch.  Float64 and float32 operations round one by one.  The rules (csrc/track_cells.h):
+ *   table   voff[t] < 0, voff[t + 1] < voff[t], voff[t + 1] > V or more than 1024 views: tflags[t] = 8; nothing is read or written through
+ *           such an entry, loss[t] and the history word included, and the track is not stepped.  tflags[t] is stored, not OR-ed.
+ *   usable  a view is usable when vflags[v] holds none of bit 0, 1, 3, 4 (what keeps sdfr_align_step from stepping a shape), its weight
+ *           (weight[v]; 1 with weight == NULL) is finite and > 0, float32 of each of its L + 5 gradient entries is finite, and -- without
+ *           share_scale -- the scale its own Adam update would leave is finite and positive.  An unusable view gets bit 2 in vflags[v] and
+ *           keeps theta, tm, tv and the yaw / trans words of its pose row.
+ *   fold    over the usable views of the track in ASCENDING view order, in float64: W = sum w_v, S_c = sum w_v g[v][c] for the latent
+ *           columns c < L and, with share_scale, column L + 4, E = sum w_v view_loss[v]; every sum STARTS FROM ITS FIRST TERM (a lone -0.0
+ *           survives).  G_c = S_c / W, loss[t] = E / W.  A track without views gets bit 0 of tflags; a track with no usable view loss[t] = 0
+ *           and bits 1 and 2, and nothing of it moves.
+ *   track   the latent z[t] is stepped by sdfr_encode_step's rule (through the unit normalisation with unit, the regulariser code_reg ||z||
+ *           without; the finite check in index order) with float32(G_c) at the rate lr; lr == 0 leaves z, m, v untouched.  With share_scale
+ *           the same Adam on scale[t] (state sm, sv) with float32(G_{L + 4}) at lr_pose[4]; a rate of 0 leaves it untouched.  If the
+ *           latent's gradient is not finite, or the stepped scale would not be finite and positive, the WHOLE track keeps everything --
+ *           latent, scale and every view's pose --; tflags[t] and the vflags of its usable views get bit 2.
+ *   views   of a stepped track: each usable view steps its own theta, tm, tv by sdfr_align_step's rule with ITS OWN gradient columns
+ *           g[v][L .. L + 4] (not scaled by w_v / W: Adam divides a constant factor out again, and a track of one view is then
+ *           sdfr_align_step in every bit) at the rates lr_pose, rate 4 taken as 0 when the scale is shared, and its pose row is rewritten.
+ *           EVERY view of a stepped track, usable or not, receives z_view[v] = z[t] (the raw latent; sdfr_align_rows normalises it) and, with
+ *           share_scale, theta[v][4] = scale[t] and the scale word of its pose row.
+ *   history[(t - 1) history_stride + track] = float32(loss[track]) (history may be NULL).  1 - beta^t as in sdfr_encode_step.
+ * scale, sm, sv are read with share_scale alone.  Refused: NULL arguments, L outside 1 .. 256, T or V outside 0 .. 65535, t < 1, a rate that is
+ * not finite, history_stride < T. */
+int sdfr_track_step(float* z, float* m, float* v, int L, int T, int unit, float* scale, float* sm, float* sv, int share_scale, const int64_t* voff, int V,
+                    const float* weight, float* theta, float* tm, float* tv, float* pose, float* z_view, const double* g, const double* view_loss,
+                    int32_t* vflags, double* loss, int32_t* tflags, float code_reg, float lr, const float* lr_pose, int t, float* history,
+                    int64_t history_stride, void* stream);
 
 /* ---- lidar clusters and rough boxes (csrc/cluster.hip, SDFR_VERSION 421) ----
  * Object proposals from a raw scan: Euclidean clusters of the (road-free) cloud and a minimum-area rectangle per cluster.  The reference

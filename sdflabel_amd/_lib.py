@@ -9,7 +9,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDFR_LIB") or os.path.join(_HERE, "lib", "libsdfr_hip.so")     # SDFR_LIB: A/B builds (tools/ab_build.sh)
 
-ABI_VERSION = 422          # include/sdfr.h SDFR_VERSION
+ABI_VERSION = 423          # include/sdfr.h SDFR_VERSION
 _lib = None
 
 # name -> (restype, argtypes); mirrors include/sdfr.h one to one
@@ -279,6 +279,10 @@ _PROTOS = {
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdfr_align_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_float, c_float, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    # one shape fitted to several views: the step that folds the views of a track (csrc/track.hip)
+    "sdfr_track_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_int,
+                                c_void_p, c_int64, c_void_p]),
     # lidar clusters and rough boxes: object proposals from a raw scan (csrc/cluster.hip)
     "sdfr_cluster_ws_bytes": (c_int64, [c_int, c_int]),
     "sdfr_lidar_clusters": (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -14,7 +14,7 @@ paper's code.  The rows are drawn from the library's own random stream (an integ
 unit_latents=True (the default here): the decoder is fed z / ||z||, for the reason pipelines.train_prior.PriorTrainer gives -- the refinement
 normalises the latent before the decoder and the CSS head projects its latent onto the unit sphere; the regulariser is then off.
 
-_fit is the one driver of the frozen-decoder fits: complete.fit_many and align.align_many hand it a _Fit of their own.
+_fit is the one driver of the frozen-decoder fits: complete.fit_many, align.align_many and track.align_tracks hand it a _Fit of their own.
 """
 import torch
 
@@ -92,6 +92,18 @@ class _Fit:
         """the step's learning-rate arguments on an iteration whose schedule factor is f"""
         return (self.lr * f,)
 
+    def group_size(self, nb):
+        """shapes of a staged group at the most, from the number the staging buffers allow"""
+        return nb
+
+    def groups(self, nb):
+        """the staged groups as (first shape, shapes): whole shapes, in order"""
+        return [(b0, min(nb, self.B - b0)) for b0 in range(0, self.B, nb)]
+
+    def step(self, step_fn, b0, n, z, m, v, Ld, unit, step_mid, g, loss, flags, code_reg, rates, t, hist, B, st):
+        """the step call of the group's n shapes from b0 on (z, m, v, loss, flags, hist: pointers at shape b0)"""
+        return step_fn(z, m, v, Ld, n, unit, *step_mid, g, loss, flags, code_reg, *rates, t, hist, B, st)
+
 
 @_lib.traced("encode_many")
 def encode_many(dsdf, samples, iters=800, rows_per_iter=8000, lr=5e-3, lr_step=None, lr_factor=0.1, clamp=0.1, code_reg=1e-4, unit_latents=True,
@@ -110,7 +122,7 @@ def encode_many(dsdf, samples, iters=800, rows_per_iter=8000, lr=5e-3, lr_step=N
 
 
 def _fit(fit, dsdf, iters, rows_per_iter, lr_step, lr_factor, clamp, code_reg, unit_latents, seed, history, staging_bytes, draw):
-    """The loop of encode_many, complete.fit_many and align.align_many over what `fit` (a _Fit) says of them.  Returns (latents, raw latents,
+    """The loop of encode_many, complete.fit_many, align.align_many and track.align_tracks over what `fit` (a _Fit) says of them.  Returns (latents, raw latents,
     loss, flags, history, unit_latents)."""
     who, B = fit.who, fit.B
     iters, k_req = int(iters), int(rows_per_iter)
@@ -166,7 +178,8 @@ def _fit(fit, dsdf, iters, rows_per_iter, lr_step, lr_factor, clamp, code_reg, u
     soff = _upload(torch.tensor(off, dtype=torch.int64), dev)
     mask_words = 0 if handle.has_ln else int(L.sdfr_decoder_mask_words(handle.h, k))
     per_shape = k * (4 * (2 * NI + 2 + fit.row_floats)) + 4 * mask_words
-    nb = max(1, min(B, int(staging_bytes) // max(per_shape, 1)))
+    nb = fit.group_size(max(1, min(B, int(staging_bytes) // max(per_shape, 1))))
+    groups = fit.groups(nb)
     n_max = nb * k
     inputs = torch.empty((n_max, NI), dtype=torch.float32, device=dev)
     J = torch.empty((n_max, NI), dtype=torch.float32, device=dev)
@@ -178,14 +191,13 @@ def _fit(fit, dsdf, iters, rows_per_iter, lr_step, lr_factor, clamp, code_reg, u
     ws = torch.empty((ws_bytes // 8,), dtype=torch.float64, device=dev)
     g = torch.empty((nb, Ld + fit.extra), dtype=torch.float64, device=dev)
     m, v = torch.zeros_like(z), torch.zeros_like(z)
-    cnts = {n: torch.full((1,), n * k, dtype=torch.int32, device=dev) for n in {nb, B % nb or nb}}
+    cnts = {n: torch.full((1,), n * k, dtype=torch.int32, device=dev) for n in {n for _, n in groups}}
     unit = 1 if unit_latents else 0
     table_flags = torch.empty((nb,), dtype=torch.int32, device=dev)          # the last call's flag output when the loop's flags are kept
     seed64 = int(seed) & 0x7FFFFFFFFFFFFFFF
     with _lib.guard(dev):
         st = _lib.stream_ptr()
-        for b0 in range(0, B, nb):
-            n = min(nb, B - b0)
+        for b0, n in groups:
             zg, so, znb, lb, fb = P(z[b0:]), P(soff[b0:]), P(zn[b0:]), P(loss[b0:]), P(flags[b0:])
             hb = P(hist[:, b0:]) if hist is not None else None
             rows_mid, rows_end, reduce_mid, step_mid = fit.group(b0, P(inputs), P(J), NI)
@@ -193,8 +205,8 @@ def _fit(fit, dsdf, iters, rows_per_iter, lr_step, lr_factor, clamp, code_reg, u
                 ck(rows_fn(P(rows), S, so, n, b0, k, 1 if draw else 0, seed64, it, zg, Ld, unit, *rows_mid, znb, fb, st), fit.rows_call)
                 decoder_rows(handle, fwd, f16, inputs, n * k, pred, J, sel, masks, idx, cnts[n], st)
                 ck(reduce_fn(P(pred), *reduce_mid, Ld, n, k, float(clamp), P(ws), ws_bytes, lb, P(g), fb, st), fit.reduce_call)
-                ck(step_fn(zg, P(m[b0:]), P(v[b0:]), Ld, n, unit, *step_mid, P(g), lb, fb, float(code_reg), *fit.rates(float(lr_factor) ** (it // lr_step)),
-                           it + 1, hb, B, st), fit.step_call)
+                ck(fit.step(step_fn, b0, n, zg, P(m[b0:]), P(v[b0:]), Ld, unit, step_mid, P(g), lb, fb, float(code_reg),
+                            fit.rates(float(lr_factor) ** (it // lr_step)), it + 1, hb, B, st), fit.step_call)
             # the latents as the decoder sees the final z (and, with iters = 0, the flags of the table)
             ck(rows_fn(None, S, so, n, b0, k, 0, seed64, 0, zg, Ld, unit, *rows_end, znb, fb if iters == 0 else P(table_flags), st), fit.rows_call)
     return out
