@@ -720,7 +720,10 @@ int sdfr_ransac_sample(int64_t seed, const int64_t* keys, const int32_t* ncnt, i
  * outputs:  found[b] (0 = the reference returns None: ncnt < 5, fewer than 5 best inliers, or a rank-deficient final procrustes),
  *   best[b] (winning hypothesis, -1 if none), n_inliers[b], scale[b], rot [B][3][3], tra [B][3];
  *   cnn_idx [B][ncap] nearest model colour per scene point; gate [B][T] bit 0 colour gate passed, bit 1 fit accepted (scored),
- *   bit 2 rank-deficient sample (s2/s1 < 1e-3); counts [B][T] inlier count per scored hypothesis, -1 otherwise. */
+ *   bit 2 rank-deficient sample (s2/s1 < 1e-3); counts [B][T] inlier count per scored hypothesis, -1 otherwise.
+ * A scene point with a NaN or infinite coordinate (the reference's SVD would raise on a sample that holds one) is nobody's inlier, and a
+ * hypothesis that samples it is scored with 0 inliers (gate 7, count 0) or, type 1 only, rejected by the rank rule (gate 5, count -1);
+ * every other hypothesis, and with it the winner and the pose, is what it would be with that point far from the model. */
 int sdfr_ransac_pose(const float* model, const float* model_cls, const int32_t* mcnt, int mcap, int model_f16, const float* scene,
                      const float* scene_cls, const int32_t* ncnt, int ncap, int B, const int32_t* idx, int64_t seed, const int64_t* keys,
                      int T, int type, float scale_model, const double* h_thr, void* ws, int32_t* found, int32_t* best, int32_t* n_inliers,

@@ -1,11 +1,33 @@
 // Float64 eigen-decomposition of a symmetric 3x3 matrix, shared by the RANSAC fits (pose.hip) and the lidar normals (normals.hip).
+// A plain function, compiled for the device by the two units and for the host by tests/pose_host/pose_host.cpp.
 #pragma once
-#include <hip/hip_runtime.h>
+#include <math.h>
 
-// eigen-decomposition of the symmetric 3x3 S (cyclic Jacobi, float64): eigenvalues descending in lam, eigenvectors as COLUMNS of V
-__device__ inline void sdfr_jacobi3(double S[3][3], double lam[3], double V[3][3]) {
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define J3_HD __host__ __device__ inline
+#else
+#define J3_HD static inline
+#endif
+
+// eigen-decomposition of the symmetric 3x3 S (cyclic Jacobi, float64): eigenvalues descending in lam, eigenvectors as COLUMNS of V.
+// The stop test and the rotations square the entries: a matrix whose largest entry lies outside [1e-100, 1e100] is first scaled by an exact
+// power of two (its eigenvalues scaled back at the end), so that neither `off` nor `1e-36 * dia` under- or overflows.  Inside that range --
+// every matrix the two users form from metric data -- nothing is scaled and every bit is as it was without the scaling.
+J3_HD void sdfr_jacobi3(double S[3][3], double lam[3], double V[3][3]) {
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    double big = 0.0, unscale = 1.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j) big = fabs(S[i][j]) > big ? fabs(S[i][j]) : big;          // (a NaN entry never wins: no scaling)
+    if (big > 0.0 && (big < 1e-100 || big > 1e100) && big <= 1.7976931348623157e308) {
+        int e = -ilogb(big);
+        e = e > 1000 ? 1000 : e;
+        const double sc = ldexp(1.0, e);
+        unscale = ldexp(1.0, -e);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) S[i][j] *= sc;
+    }
     for (int sweep = 0; sweep < 32; ++sweep) {
         const double off = S[0][1] * S[0][1] + S[0][2] * S[0][2] + S[1][2] * S[1][2];
         const double dia = S[0][0] * S[0][0] + S[1][1] * S[1][1] + S[2][2] * S[2][2];
@@ -40,7 +62,7 @@ __device__ inline void sdfr_jacobi3(double S[3][3], double lam[3], double V[3][3
             if (S[o[j]][o[j]] < S[o[j + 1]][o[j + 1]]) { const int x = o[j]; o[j] = o[j + 1]; o[j + 1] = x; }
     double W[3][3];
     for (int i = 0; i < 3; ++i) {
-        lam[i] = S[o[i]][o[i]];
+        lam[i] = S[o[i]][o[i]] * unscale;
         for (int k = 0; k < 3; ++k) W[k][i] = V[k][o[i]];
     }
     for (int i = 0; i < 3; ++i)

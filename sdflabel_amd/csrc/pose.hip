@@ -13,12 +13,7 @@
 //   final     means and cross-covariance of the inliers' colour-NN correspondences in float64 (fixed order), final fit model -> scene
 // Every reduction is fixed-order or integer, so a crop gives the same bits in any batch.
 #include "sdfr_common.h"
-#include "jacobi3.h"
-#include <hip/hip_fp16.h>
-
-#define RS_TPB 256      // threads per workgroup (every kernel)
-#define RS_HG 8         // passing hypotheses per scoring workgroup (registers: 3 + 2 per hypothesis)
-#define RS_TRANS 12     // float32 [3][4] = [rot*scale | tra] of a hypothesis
+#include "pose_cells.h"       // RS_TPB, RS_HG, RS_TRANS and every per-element rule (rs_*, pose_sample_fit)
 
 namespace {
 
@@ -48,50 +43,21 @@ static size_t ws_layout(int B, int ncap, int T, char* base, Ws* w) {
 }
 
 // ---- device sampler -----------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint64_t rs_mix64(uint64_t z) {          // splitmix64 finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// draw k of hypothesis t, attempt c: hi 32 bits of the hash scaled to [0, n) by multiply-shift.  Repeats of an earlier draw are rejected
-// (next attempt); after 64 attempts the value steps forward to the next unused index (never reached in practice, keeps the loop bounded).
+// rs_sample_draw (pose_cells.h): the 4 distinct indices of (seed, key, t)
 __global__ __launch_bounds__(RS_TPB) void rs_sample_kernel(uint64_t seed, const int64_t* __restrict__ keys, const int32_t* __restrict__ ncnt,
                                                          int T, int32_t* __restrict__ idx) {
     const int b = blockIdx.y, t = blockIdx.x * RS_TPB + threadIdx.x;
     if (t >= T) return;
     const int n = ncnt[b];
     const uint64_t key = keys ? (uint64_t)keys[b] : (uint64_t)b;
-    const uint64_t hk = rs_mix64(seed ^ rs_mix64(key * 0x9E3779B97F4A7C15ull + 1ull));
-    int d[4] = {0, 0, 0, 0};
-    if (n >= 4) {
-        for (int k = 0; k < 4; ++k) {
-            int x = 0;
-            for (int c = 0;; ++c) {
-                const uint64_t h = rs_mix64(hk ^ (((uint64_t)t << 16) | ((uint64_t)k << 8) | (uint64_t)c));
-                x = (int)(((h >> 32) * (uint64_t)n) >> 32);
-                bool rep = false;
-                for (int q = 0; q < k; ++q) rep |= d[q] == x;
-                if (!rep) break;
-                if (c == 63) {
-                    for (;;) {
-                        x = x + 1 == n ? 0 : x + 1;
-                        rep = false;
-                        for (int q = 0; q < k; ++q) rep |= d[q] == x;
-                        if (!rep) break;
-                    }
-                    break;
-                }
-            }
-            d[k] = x;
-        }
-    }
+    int d[4];
+    rs_sample_draw(rs_sample_key(seed, key), t, n, d);
     int4 v = make_int4(d[0], d[1], d[2], d[3]);
     *(int4*)(idx + ((size_t)b * T + t) * 4) = v;
 }
 
 // ---- colour-NN table ------------------------------------------------------------------------------------------------------------------
-// KDTree(model_cls).query in float64: rdist = (dx^2 + dy^2) + dz^2, distance sqrt(rdist); ties go to the lowest model index.
+// KDTree(model_cls).query in float64 (rs_cnn_step), distance sqrt(rdist); ties go to the lowest model index.
 __global__ __launch_bounds__(RS_TPB) void rs_cnn_kernel(const float* __restrict__ mcls, const int32_t* __restrict__ mcnt, int mcap,
                                                       const float* __restrict__ scls, const int32_t* __restrict__ ncnt, int ncap,
                                                       int32_t* __restrict__ cnn_idx, double* __restrict__ cnn_d) {
@@ -110,9 +76,7 @@ __global__ __launch_bounds__(RS_TPB) void rs_cnn_kernel(const float* __restrict_
         __syncthreads();
         const int n = M - base < RS_TPB ? M - base : RS_TPB;
         for (int k = 0; k < n; ++k) {
-            const double dx = qx - (double)tx[k], dy = qy - (double)ty[k], dz = qz - (double)tz[k];
-            const double d2 = dx * dx + dy * dy + dz * dz;
-            if (d2 < best) { best = d2; bi = base + k; }
+            rs_cnn_step(qx, qy, qz, tx[k], ty[k], tz[k], base + k, &best, &bi);
         }
         __syncthreads();
     }
@@ -120,69 +84,6 @@ __global__ __launch_bounds__(RS_TPB) void rs_cnn_kernel(const float* __restrict_
         cnn_idx[(size_t)b * ncap + p] = bi;
         cnn_d[(size_t)b * ncap + p] = sqrt(best);
     }
-}
-
-// ---- fits ------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double rs_round(double x, bool f16) {     // a value stored in the numpy dtype of the array it belongs to
-    return f16 ? (double)__half2float(__float2half_rn((float)x)) : (double)(float)x;
-}
-
-// H = sum to_c from_c^T (H[i][j] = sum to_i from_j): the reference's cross-correlation (kabsch) / covariance times N (procrustes).
-// R = U diag(1, 1, det V) V^T with u1 = H v1 / s1, u2 = H v2 / s2 (made orthogonal to u1), u3 = u1 x u2 -- the unique rotation both
-// reference fits return whenever rank(H) >= 2, whatever sign convention their SVD picked.  s3' = u3 . H v3 (signed).
-// type 1 (procrustes): returns false when numpy's matrix_rank of the float32 covariance (tol = s1 * 3 * eps_f32) is below 2;
-// c = (s1 + s2 + det V s3') / sum |from_c|^2 (= (d * S.diag).sum() / sigma_from).  Translation: kabsch  R(pm - cm) - R pm + pm,
-// procrustes  mean_to - c R mean_from.
-__device__ bool rs_fit(const double H[3][3], const double mf[3], const double mt[3], double sig_from, int type, double R[3][3], double* c,
-                       double t[3], double* s_ratio) {
-    double S[3][3], lam[3], V[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) S[i][j] = H[0][i] * H[0][j] + H[1][i] * H[1][j] + H[2][i] * H[2][j];
-    sdfr_jacobi3(S, lam, V);
-    double U[3][3];
-    const double s1 = sqrt(lam[0] > 0.0 ? lam[0] : 0.0), s2 = sqrt(lam[1] > 0.0 ? lam[1] : 0.0);
-    for (int k = 0; k < 2; ++k)
-        for (int i = 0; i < 3; ++i) U[i][k] = H[i][0] * V[0][k] + H[i][1] * V[1][k] + H[i][2] * V[2][k];
-    double n1 = sqrt(U[0][0] * U[0][0] + U[1][0] * U[1][0] + U[2][0] * U[2][0]);
-    if (!(n1 > 0.0)) { U[0][0] = 1.0; U[1][0] = 0.0; U[2][0] = 0.0; n1 = 1.0; }
-    for (int i = 0; i < 3; ++i) U[i][0] /= n1;
-    const double d12 = U[0][0] * U[0][1] + U[1][0] * U[1][1] + U[2][0] * U[2][1];
-    for (int i = 0; i < 3; ++i) U[i][1] -= d12 * U[i][0];
-    double n2 = sqrt(U[0][1] * U[0][1] + U[1][1] * U[1][1] + U[2][1] * U[2][1]);
-    if (!(n2 > 1e-300)) {                              // rank 1: any unit vector orthogonal to u1
-        const int a = fabs(U[0][0]) < 0.6 ? 0 : 1;
-        double e[3] = {0.0, 0.0, 0.0};
-        e[a] = 1.0;
-        const double d = e[0] * U[0][0] + e[1] * U[1][0] + e[2] * U[2][0];
-        for (int i = 0; i < 3; ++i) U[i][1] = e[i] - d * U[i][0];
-        n2 = sqrt(U[0][1] * U[0][1] + U[1][1] * U[1][1] + U[2][1] * U[2][1]);
-    }
-    for (int i = 0; i < 3; ++i) U[i][1] /= n2;
-    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-    U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-    U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-    const double detV = V[0][0] * (V[1][1] * V[2][2] - V[1][2] * V[2][1]) - V[0][1] * (V[1][0] * V[2][2] - V[1][2] * V[2][0]) +
-                        V[0][2] * (V[1][0] * V[2][1] - V[1][1] * V[2][0]);
-    const double sv = detV < 0.0 ? -1.0 : 1.0;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) R[i][j] = U[i][0] * V[j][0] + U[i][1] * V[j][1] + sv * U[i][2] * V[j][2];
-    *s_ratio = s1 > 0.0 ? s2 / s1 : 0.0;
-    if (type == 1) {
-        if (!(s2 > s1 * 3.0 * 1.1920928955078125e-07 /* float32 eps */)) return false;
-        double hv[3];
-        for (int i = 0; i < 3; ++i) hv[i] = H[i][0] * V[0][2] + H[i][1] * V[1][2] + H[i][2] * V[2][2];
-        const double s3 = U[0][2] * hv[0] + U[1][2] * hv[1] + U[2][2] * hv[2];
-        *c = (s1 + s2 + sv * s3) / sig_from;
-        for (int i = 0; i < 3; ++i) t[i] = mt[i] - *c * (R[i][0] * mf[0] + R[i][1] * mf[1] + R[i][2] * mf[2]);
-    } else {
-        *c = 1.0;
-        for (int i = 0; i < 3; ++i) {
-            const double a = R[i][0] * (mt[0] - mf[0]) + R[i][1] * (mt[1] - mf[1]) + R[i][2] * (mt[2] - mf[2]);
-            const double bb = R[i][0] * mt[0] + R[i][1] * mt[1] + R[i][2] * mt[2];
-            t[i] = a - bb + mt[i];
-        }
-    }
-    return true;
 }
 
 // ---- hypotheses: gate, fit, compaction ---------------------------------------------------------------------------------------------
@@ -213,44 +114,23 @@ __global__ __launch_bounds__(RS_TPB) void rs_hyp_kernel(const float* __restrict_
                     for (int k = 0; k < 4; ++k) g &= !(cnn_d[(size_t)b * ncap + ii[k]] > nocs_thr);
                     if (g) {
                         flag = 1;
-                        // from = the 4 scene points (float32), to = their colour-NN model points (the model's dtype); numpy means: float32
-                        // sums in order, / 4 in float32, stored in the dtype; centred values stored in the dtype
-                        float fp[4][3], tp[4][3];
+                        // from = the 4 scene points (float32), to = their colour-NN model points (the model's dtype)
+                        float fp[4][3], tp[4][3], h[RS_TRANS];
                         for (int k = 0; k < 4; ++k) {
                             const float* s = scene + ((size_t)b * ncap + ii[k]) * 3;
                             const float* m = model + ((size_t)b * mcap + cnn_idx[(size_t)b * ncap + ii[k]]) * 3;
                             for (int d = 0; d < 3; ++d) { fp[k][d] = s[d]; tp[k][d] = m[d]; }
                         }
-                        double mf[3], mt[3], H[3][3], fc[4][3], tc[4][3], sig = 0.0;
-                        for (int d = 0; d < 3; ++d) {
-                            const float sf = ((fp[0][d] + fp[1][d]) + fp[2][d]) + fp[3][d];
-                            const float st = ((tp[0][d] + tp[1][d]) + tp[2][d]) + tp[3][d];
-                            mf[d] = (double)(sf / 4.0f);
-                            mt[d] = rs_round((double)(st / 4.0f), f16);
-                        }
-                        for (int k = 0; k < 4; ++k)
-                            for (int d = 0; d < 3; ++d) {
-                                fc[k][d] = rs_round((double)fp[k][d] - mf[d], false);
-                                tc[k][d] = rs_round((double)tp[k][d] - mt[d], f16);
-                                sig += fc[k][d] * fc[k][d];
-                            }
-                        for (int i = 0; i < 3; ++i)
-                            for (int j = 0; j < 3; ++j) H[i][j] = ((tc[0][i] * fc[0][j] + tc[1][i] * fc[1][j]) + tc[2][i] * fc[2][j]) + tc[3][i] * fc[3][j];
-                        double R[3][3], c, tr[3], ratio;
-                        if (rs_fit(H, mf, mt, sig, type, R, &c, tr, &ratio) && !((float)c > 3.0f)) {
-                            flag |= 2;
+                        int bits;
+                        if (pose_sample_fit(fp, tp, f16, type, h, &bits)) {
                             cnt = 0;
                             pass = true;
                             float* hp = w.hyp + ((size_t)b * T + t) * RS_TRANS;
-                            const float cf = (float)c;
-                            float4 r0 = make_float4((float)R[0][0] * cf, (float)R[0][1] * cf, (float)R[0][2] * cf, (float)tr[0]);
-                            float4 r1 = make_float4((float)R[1][0] * cf, (float)R[1][1] * cf, (float)R[1][2] * cf, (float)tr[1]);
-                            float4 r2 = make_float4((float)R[2][0] * cf, (float)R[2][1] * cf, (float)R[2][2] * cf, (float)tr[2]);
-                            *(float4*)(hp) = r0;
-                            *(float4*)(hp + 4) = r1;
-                            *(float4*)(hp + 8) = r2;
+                            *(float4*)(hp) = make_float4(h[0], h[1], h[2], h[3]);
+                            *(float4*)(hp + 4) = make_float4(h[4], h[5], h[6], h[7]);
+                            *(float4*)(hp + 8) = make_float4(h[8], h[9], h[10], h[11]);
                         }
-                        if (ratio < 1e-3) flag |= 4;           // rank-deficient sample (diagnostic)
+                        flag |= bits;
                     }
                 }
             }
@@ -275,16 +155,10 @@ __global__ __launch_bounds__(RS_TPB) void rs_hyp_kernel(const float* __restrict_
 }
 
 // ---- scoring ----------------------------------------------------------------------------------------------------------------------------
-// the reference's transformed scene point: (trans[:, :3] @ scene.T).T + trans[:, 3] in float32, separate roundings in the sum's order
-__device__ __forceinline__ float3 rs_transform(const float* __restrict__ h, float x, float y, float z) {
-    return make_float3(((h[0] * x + h[1] * y) + h[2] * z) + h[3], ((h[4] * x + h[5] * y) + h[6] * z) + h[7],
-                       ((h[8] * x + h[9] * y) + h[10] * z) + h[11]);
-}
-
 // nearest model point of HN transformed points, searched on float32 squared distances (first index on exact ties); model points
 // stream through the workgroup's LDS tiles.  Every thread of the workgroup must call it (barriers).
 template <int HN>
-__device__ __forceinline__ void rs_nn_search(const float3 (&tp)[HN], int (&bi)[HN], const float* __restrict__ mp, int M, float4* tile) {
+__device__ __forceinline__ void rs_nn_search(const PoseV3 (&tp)[HN], int (&bi)[HN], const float* __restrict__ mp, int M, float4* tile) {
     float bd[HN];
     for (int h = 0; h < HN; ++h) { bd[h] = INFINITY; bi[h] = 0; }
     const int tid = threadIdx.x;
@@ -297,24 +171,11 @@ __device__ __forceinline__ void rs_nn_search(const float3 (&tp)[HN], int (&bi)[H
             const float4 m = tile[k];
 #pragma unroll
             for (int h = 0; h < HN; ++h) {
-                const float dx = tp[h].x - m.x, dy = tp[h].y - m.y, dz = tp[h].z - m.z;
-                const float d2 = __fmaf_rn(dx, dx, __fmaf_rn(dy, dy, dz * dz));
-                if (d2 < bd[h]) { bd[h] = d2; bi[h] = base + k; }
+                rs_nn_step(tp[h], m.x, m.y, m.z, base + k, &bd[h], &bi[h]);
             }
         }
         __syncthreads();
     }
-}
-
-// the inlier decision of step 5 for the winner nn: KDTree distance recomputed in float64 (< metric_thr), colour norm in float32
-__device__ __forceinline__ bool rs_inlier(float3 tp, int nn, const float* __restrict__ mp, const float* __restrict__ mc, float sx, float sy,
-                                          float sz, double metric_thr, float nocs_thr32) {
-    const double dx = (double)tp.x - (double)mp[(size_t)nn * 3], dy = (double)tp.y - (double)mp[(size_t)nn * 3 + 1],
-                 dz = (double)tp.z - (double)mp[(size_t)nn * 3 + 2];
-    const double d = sqrt(dx * dx + dy * dy + dz * dz);
-    const float cx = sx - mc[(size_t)nn * 3], cy = sy - mc[(size_t)nn * 3 + 1], cz = sz - mc[(size_t)nn * 3 + 2];
-    const float dc = sqrtf(cx * cx + cy * cy + cz * cz);
-    return d < metric_thr && dc < nocs_thr32;
 }
 
 __global__ __launch_bounds__(RS_TPB) void rs_score_kernel(const float* __restrict__ model, const float* __restrict__ mcls,
@@ -330,7 +191,7 @@ __global__ __launch_bounds__(RS_TPB) void rs_score_kernel(const float* __restric
     const int p = blockIdx.x * RS_TPB + tid;
     const float* s = scene + ((size_t)b * ncap + (p < N ? p : 0)) * 3;
     const float sx = s[0], sy = s[1], sz = s[2];
-    float3 tp[RS_HG];
+    PoseV3 tp[RS_HG];
     int hid[RS_HG];
     for (int h = 0; h < RS_HG; ++h) {
         hid[h] = w.plist[(size_t)b * T + g0 + (h < nh ? h : 0)];
@@ -360,7 +221,7 @@ __global__ __launch_bounds__(RS_TPB) void rs_select_kernel(const int32_t* __rest
     int bc = 0, bt = -1;             // the reference starts from an empty inlier set: a count must be > 0 to be taken
     for (int t = tid; t < T; t += RS_TPB) {
         const int c = counts[(size_t)b * T + t];
-        if (c > bc) { bc = c; bt = t; }
+        if (rs_select_takes(c, bc)) { bc = c; bt = t; }
     }
     sc[tid] = bc;
     st[tid] = bt;
@@ -368,7 +229,7 @@ __global__ __launch_bounds__(RS_TPB) void rs_select_kernel(const int32_t* __rest
     for (int o = RS_TPB / 2; o > 0; o >>= 1) {
         if (tid < o) {
             const int c2 = sc[tid + o], t2 = st[tid + o];
-            if (c2 > sc[tid] || (c2 == sc[tid] && t2 >= 0 && (st[tid] < 0 || t2 < st[tid]))) { sc[tid] = c2; st[tid] = t2; }
+            if (rs_select_folds(c2, t2, sc[tid], st[tid])) { sc[tid] = c2; st[tid] = t2; }
         }
         __syncthreads();
     }
@@ -391,7 +252,7 @@ __global__ __launch_bounds__(RS_TPB) void rs_mask_kernel(const float* __restrict
         return;
     }
     const float* s = scene + ((size_t)b * ncap + (p < N ? p : 0)) * 3;
-    float3 tp[1] = {rs_transform(w.hyp + ((size_t)b * T + bt) * RS_TRANS, s[0], s[1], s[2])};
+    PoseV3 tp[1] = {rs_transform(w.hyp + ((size_t)b * T + bt) * RS_TRANS, s[0], s[1], s[2])};
     const float* mp = model + (size_t)b * mcap * 3;
     int bi[1];
     rs_nn_search<1>(tp, bi, mp, M, tile);
@@ -434,29 +295,17 @@ __global__ __launch_bounds__(RS_TPB) void rs_final_kernel(const float* __restric
             if (mk[p]) {
                 const float* s = scene + ((size_t)b * ncap + p) * 3;
                 const float* m = model + ((size_t)b * mcap + cnn_idx[(size_t)b * ncap + p]) * 3;
-                for (int d = 0; d < 3; ++d) { v6[d] += (double)m[d]; v6[3 + d] += (double)s[d]; }
-                v6[6] += 1.0;
+                rs_final_sums(m, s, v6);
             }
         rs_block_sum<7>(v6, red);
-        const double n = v6[6];
         double mf[3], mt[3];
-        for (int d = 0; d < 3; ++d) {
-            mf[d] = rs_round(v6[d] / n, f16);          // numpy means in the arrays' dtypes (model: float16 / float32, scene: float32)
-            mt[d] = rs_round(v6[3 + d] / n, false);
-        }
+        rs_final_means(v6, f16, mf, mt);
         double v10[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         for (int p = tid; p < N; p += RS_TPB)
             if (mk[p]) {
                 const float* s = scene + ((size_t)b * ncap + p) * 3;
                 const float* m = model + ((size_t)b * mcap + cnn_idx[(size_t)b * ncap + p]) * 3;
-                double fc[3], tc[3];
-                for (int d = 0; d < 3; ++d) {
-                    fc[d] = rs_round((double)m[d] - mf[d], f16);
-                    tc[d] = rs_round((double)s[d] - mt[d], false);
-                }
-                for (int i = 0; i < 3; ++i)
-                    for (int j = 0; j < 3; ++j) v10[i * 3 + j] += tc[i] * fc[j];
-                v10[9] += (fc[0] * fc[0] + fc[1] * fc[1]) + fc[2] * fc[2];
+                rs_final_cov(m, s, mf, mt, f16, v10);
             }
         rs_block_sum<10>(v10, red);
         if (tid == 0) {

@@ -120,6 +120,34 @@ def device_sample(ncnt, T, seed=0, keys=None):
     return idx
 
 
+def workspace_layout(B, ncap, T):
+    """Python mirror of ws_layout (csrc/pose.hip): ([(name, bytes, dtype, shape), ...], total bytes) of the workspace's 256-byte aligned
+    segments in their order.  The total equals sdfr_ransac_ws_bytes(B, ncap, T)."""
+    al = lambda n: (n + 255) & ~255
+    segs = [("cnn_d", al(8 * B * ncap), torch.float64, (B, ncap)), ("hyp", al(4 * 12 * B * T), torch.float32, (B, T, 12)),
+            ("plist", al(4 * B * T), torch.int32, (B, T)), ("pcount", al(4 * B), torch.int32, (B,)), ("mask", al(4 * B * ncap), torch.int32, (B, ncap))]
+    return segs, sum(s[1] for s in segs)
+
+
+def workspace_views(out):
+    """Typed views of a ransac_pose result's workspace (out["_keep"]), for tests and diagnostics: cnn_d [B][ncap] float64 (distance to the
+    nearest model colour), hyp [B][T][12] float32 ([rot*scale | tra] of a hypothesis), plist [B][T] / pcount [B] (the scored hypotheses in
+    order), mask [B][ncap] (the winner's inlier mask).  Defined entries only: hyp rows of scored hypotheses (counts >= 0), plist[:pcount],
+    cnn_d[:N] and mask[:N] of a crop; everything else is whatever the allocator left there."""
+    (B, ncap), T, ws = out["cnn_idx"].shape, out["gate"].shape[1], out["_keep"]
+    segs, total = workspace_layout(B, ncap, T)
+    if ws.numel() < total:
+        raise ValueError("workspace_views: the workspace has %d bytes, the layout needs %d" % (ws.numel(), total))
+    views, at = {}, 0
+    for name, nbytes, dtype, shape in segs:
+        n = 1
+        for s in shape:
+            n *= s
+        views[name] = ws[at:at + n * torch.empty((), dtype=dtype).element_size()].view(dtype).view(shape)
+        at += nbytes
+    return views
+
+
 @_lib.traced("ransac_pose")
 def ransac_pose(model_pts, model_cls, scene_pts, scene_cls, type="kabsch", scale_model=1.0, sampler="device", seed=0, keys=None, idx=None,
                 metric_distance_threshold=0.15, nocs_distance_threshold=0.15, iterations=None, device=None):
