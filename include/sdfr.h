@@ -34,7 +34,7 @@ extern "C" {
 #define SDFR_TRACE_LEVELS 6     /* most speculation levels of a sphere-tracing march schedule (sdfr_trace_march) */
 #define SDFR_TRACE_COUNTERS 32  /* int32 device counters of a march / a cone march (zeroed by sdfr_trace_setup / sdfr_trace_cone) */
 
-#define SDFR_VERSION 423        /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
+#define SDFR_VERSION 424       /* what sdfr_version() of the library this header belongs to returns; a binding compares the two */
 
 /* ABI version: bumped whenever an exported signature or a buffer size changes (300: the r04 argument lists of sdfr_trace_march /
  * sdfr_trace_cone and the 32-word SDFR_TRACE_COUNTERS; 400: the r06 fused entry points below -- sdfr_params_plan, sdfr_band_select_ex,
@@ -52,7 +52,7 @@ extern "C" {
  * sdfr_bound_*; 420: pose and shape fitted to one view, sdfr_align_*;
  * 421: lidar clusters and rough boxes, sdfr_cluster_* and sdfr_lidar_clusters; 422: band selection and tile ranking in one launch,
  * sdfr_mlp_forward_balanced_deferred and sdfr_band_select_rank;
- * 423: one shape fitted to several views, sdfr_track_step).  A caller built
+ * 423: one shape fitted to several views, sdfr_track_step; 424: choosing a fit's start, sdfr_search_*).  A caller built
  * against another header must refuse the library. */
 int sdfr_version(void);
 /* 0 for the product library.  Bit 0: built with SDFR_EXPERIMENT (kernel geometry / option A/B build of tools/ab_variant.sh);
@@ -1356,6 +1356,46 @@ int sdfr_track_step(float* z, float* m, float* v, int L, int T, int unit, float*
                     const float* weight, float* theta, float* tm, float* tv, float* pose, float* z_view, const double* g, const double* view_loss,
                     int32_t* vflags, double* loss, int32_t* tflags, float code_reg, float lr, const float* lr_pose, int t, float* history,
                     int64_t history_stride, void* stream);
+
+/* ---- choosing a fit's start: scored candidates (csrc/search.hip, SDFR_VERSION 424) ----
+ *
+ * The frozen-decoder fits are local: from a far start they end in another minimum.  A START is a candidate (latent, pose) for one shape; many
+ * starts share one shape's samples.  The three entry points score all starts of all shapes on the SAME drawn rows per shape, by the loss
+ * alone, and rank them per shape:  sdfr_search_rows -> a decoder forward (no Jacobian) -> sdfr_search_reduce -> sdfr_search_select.  All
+ * pointers are device pointers; no atomics, no memset, no host synchronisation, the same bits on every run, and a start's results depend
+ * neither on N nor on its position in the batch.  Float64 and float32 operations round one by one.  csrc/search_cells.h holds the
+ * per-element rules; DESIGN.md 7p.
+ *
+ * sdfr_search_rows: the rows kernel of the fits with one indirection.  Start s < N reads the samples of shape own[s] (int32 [N]; samples
+ *   [S][5] and soff int64 [B + 1] as sdfr_bound_rows / sdfr_align_rows take them), with its own latent z[s] and, with pose != NULL, its own
+ *   pose row pose[s][6].  The draw's hash takes shape0 + own[s], not s: every start of a shape sees the same drawn samples in the same
+ *   order.  pose == NULL: lattice-frame interval rows, the rule of sdfr_bound_rows.  pose != NULL: camera-frame rows through the start's
+ *   pose, the rule of sdfr_align_rows -- NaN bounds for a row that leaves the cube, bit 4 for an unusable pose --; cam [N k][3] may be NULL,
+ *   then nothing is written for it.  own[s] outside [0, B): flags[s] = 8 and zero rows; nothing is read through it.  The other flags are
+ *   those of sdfr_bound_rows / sdfr_align_rows, per start.  Writes inputs [N k][L + 3], lo, hi [N k], zn [N][L], flags [N]; inputs == NULL:
+ *   zn and flags only.  With own = 0 .. B - 1 every output equals that of sdfr_bound_rows / sdfr_align_rows bit for bit.  N <= 65535,
+ *   shape0 + B <= 65535.  One launch.
+ *
+ * sdfr_search_reduce: the loss alone, per start: loss[s] = the mean of e over the ok rows of start s, by the row rule of sdfr_bound_reduce
+ *   on p (pose == NULL) or of sdfr_align_reduce on float32(pose[s][5] p), summed in sdfr_encode_reduce's order (the same kernels with no
+ *   gradient columns) -- the loss word of those calls on the same pred, lo, hi, pose in every bit.  No J is read.  A start without an ok row
+ *   gets loss 0 and bit 1 of flags[s] (flags [N] on entry and exit).  ws: sdfr_search_ws_bytes(N, k) = N chunks 2 float64 words, aligned
+ *   to 8 (-1 for sizes the kernels refuse).  Two launches.
+ *
+ * sdfr_search_select: grid (B), one workgroup a shape.  Shape b owns starts coff[b] .. coff[b + 1] - 1 (int64 [B + 1]).  A start is USABLE if
+ *   its flags hold none of bit 0, 1, 3, 4 and its loss is finite.  The usable starts are ranked by (loss as float64, start index) ascending;
+ *   equal losses, -0.0 == 0.0 included, go to the lower index.  order [B][keep] int32: the global start index of rank r for
+ *   r < min(keep, usable), -1 beyond; count [B] int32: that minimum.  coff[b] < 0, coff[b + 1] < coff[b], coff[b + 1] > N or more than 4096
+ *   starts: count[b] = -1 and a row of -1; nothing is read through such an entry.  A shape without starts gets count 0.  1 <= keep <= 64.
+ *   One launch. */
+int sdfr_search_rows(const float* samples, int64_t S, const int64_t* soff, int B, const int32_t* own, int N, int shape0, int64_t k, int draw,
+                     int64_t seed, int64_t iter, const float* z, int L, int unit, const float* pose, float* inputs, float* cam, float* lo, float* hi,
+                     float* zn, int32_t* flags, void* stream);
+int64_t sdfr_search_ws_bytes(int N, int64_t k);
+int sdfr_search_reduce(const float* pred, const float* lo, const float* hi, const float* pose, int N, int64_t k, float clamp, void* ws,
+                       int64_t ws_bytes, double* loss, int32_t* flags, void* stream);
+int sdfr_search_select(const double* loss, const int32_t* flags, const int64_t* coff, int B, int64_t N, int keep, int32_t* order, int32_t* count,
+                       void* stream);
 
 /* ---- lidar clusters and rough boxes (csrc/cluster.hip, SDFR_VERSION 421) ----
  * Object proposals from a raw scan: Euclidean clusters of the (road-free) cloud and a minimum-area rectangle per cluster.  The reference

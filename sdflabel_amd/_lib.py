@@ -9,7 +9,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDFR_LIB") or os.path.join(_HERE, "lib", "libsdfr_hip.so")     # SDFR_LIB: A/B builds (tools/ab_build.sh)
 
-ABI_VERSION = 423          # include/sdfr.h SDFR_VERSION
+ABI_VERSION = 424         # include/sdfr.h SDFR_VERSION
 _lib = None
 
 # name -> (restype, argtypes); mirrors include/sdfr.h one to one
@@ -283,6 +283,12 @@ _PROTOS = {
     "sdfr_track_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_int,
                                 c_void_p, c_int64, c_void_p]),
+    # choosing a fit's start: many starts on one shape's rows, the loss alone, the ranking per shape (csrc/search.hip)
+    "sdfr_search_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_int, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdfr_search_ws_bytes": (c_int64, [c_int, c_int64]),
+    "sdfr_search_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sdfr_search_select": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     # lidar clusters and rough boxes: object proposals from a raw scan (csrc/cluster.hip)
     "sdfr_cluster_ws_bytes": (c_int64, [c_int, c_int]),
     "sdfr_lidar_clusters": (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -42,6 +42,7 @@ class Aligned:
     def __init__(self, latents, raw_latents, theta, loss, flags, history, samples, unit_latents):
         self.latents, self.raw_latents, self.theta, self.loss, self.flags, self.history = latents, raw_latents, theta, loss, flags, history
         self.samples, self.unit_latents = samples, unit_latents
+        self.found = self.chosen = self.fits = None                # align_many(search=...): the search.Found, the chosen rank, every kept start's fit
         self.params = [{"yaw": theta[b, 0:1], "trans": theta[b, 1:4], "scale": theta[b, 4:5], "latent": latents[b]} for b in range(int(theta.shape[0]))]
 
 
@@ -71,6 +72,13 @@ def align_samples_many(clouds, normals=None, origin=(0.0, 0.0, 0.0), free_rows=4
     if dev.type != "cuda":
         raise _lib.SdfrError("align_samples_many runs on the GPU only; there is no CPU fallback")
     return _view_rows("align_samples_many", "sdfr_align_samples", clouds, normals, origin, F, eta, s_max, seed, dev)
+
+
+def _make_samples(clouds, normals, origin, F, eta, s_max, seed, dev):
+    """the observation rows align_many makes of its clouds: normals=None estimates them with frame.lidar_normals on each cloud"""
+    if normals is None:
+        normals = [_cloud_normals(c) if len(c) else torch.zeros((0, 3), dtype=torch.float64, device=dev) for c in _on_device(clouds, torch.float32, dev)]
+    return align_samples_many(clouds, normals, origin, F, eta, s_max, seed, _device=dev)
 
 
 def _rates(fit, lr, lr_pose):
@@ -140,7 +148,7 @@ class _PoseFit(_Fit):
 @_lib.traced("align_many")
 def align_many(dsdf, params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0), free_rows=4, eta=0.02, s_max=1.0, seed=0, fit=("yaw", "trans", "latent"),
                iters=200, rows_per_iter=2000, lr=5e-3, lr_pose=1e-2, lr_step=None, lr_factor=0.1, clamp=0.2, code_reg=1e-4, unit_latents=True,
-               history=False, staging_bytes=STAGING_BYTES, draw=None, samples=None):
+               history=False, staging_bytes=STAGING_BYTES, draw=None, samples=None, *, search=None):
     """Fit pose and shape of every annotation to its lidar cloud alone, under the frozen decoder `dsdf`.
 
     params_list: per annotation the start {'yaw', 'trans', 'scale', 'latent'} (any rough box with a latent, or what the refinement leaves);
@@ -156,11 +164,21 @@ def align_many(dsdf, params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0), 
     little else: with scale free the fit slides along scale * trans_z = const and ends wherever the prior's idea of the hidden side puts it.
     Fit the scale when the start's scale is worse than its depth, or when the cloud wraps the object.
 
+    search: None, or a dict for search.search_poses -- `codes` (a codebook [C][L]), `yaws` (yaw offsets, default (0, pi)), `keep` (default 2),
+    `rows` (default rows_per_iter) --: the starts of every shape (codes x yaw offsets on the given box) are scored and ranked first, the fit
+    runs on B x keep copies of the shapes from the kept starts (the latents of params_list are not used), and search.choose returns, per
+    shape, the copy whose fit ended with the lowest loss.  The Aligned then holds the chosen fits, `.found` the search.Found, `.chosen` int64
+    [B] the chosen rank (-1: none usable, rank 0 is returned) and `.fits` the Aligned of all B x keep fits, shape-major.
+
     Returns an Aligned.  See the module docstring for what the defaults are."""
     params_list = list(params_list)
     B, F = len(params_list), int(free_rows)
     lr_lat, lr_p = _rates(fit, lr, lr_pose)
     _check_view("align_many", B, F, eta, s_max)
+    if search is not None:
+        return _align_searched(dsdf, params_list, clouds, samples, dict(search), dict(normals=normals, origin=origin, free_rows=F, eta=eta, s_max=s_max, seed=seed),
+                               dict(fit=fit, iters=iters, rows_per_iter=rows_per_iter, lr=lr, lr_pose=lr_pose, lr_step=lr_step, lr_factor=lr_factor,
+                                    clamp=clamp, code_reg=code_reg, unit_latents=unit_latents, history=history, staging_bytes=staging_bytes, draw=draw))
     make = None
     if samples is None:
         clouds = list(clouds)
@@ -170,10 +188,7 @@ def align_many(dsdf, params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0), 
             raise ValueError("align_many: %d parameter sets, %d normal arrays" % (B, len(normals)))
 
         def make(dev):
-            nrm = normals
-            if nrm is None:
-                nrm = [_cloud_normals(c) if len(c) else torch.zeros((0, 3), dtype=torch.float64, device=dev) for c in _on_device(clouds, torch.float32, dev)]
-            return align_samples_many(clouds, nrm, origin, F, eta, s_max, seed, _device=dev)
+            return _make_samples(clouds, normals, origin, F, eta, s_max, seed, dev)
     else:
         samples = [samples] if isinstance(samples, BoundSamples) else list(samples)
         if len(samples) != B:
@@ -181,3 +196,27 @@ def align_many(dsdf, params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0), 
     f = _PoseFit(params_list, samples, make, lr_lat, lr_p, seed)
     zn, z, loss, flags, hist, unit = _fit(f, dsdf, iters, rows_per_iter, lr_step, lr_factor, clamp, code_reg, unit_latents, seed, history, staging_bytes, draw)
     return Aligned(zn, z, f.theta, loss, flags, hist, f.samples, unit)
+
+
+def _align_searched(dsdf, params_list, clouds, samples, search, view_kw, kw):
+    """align_many with search=: search.search_poses, the fit of every kept start, search.choose"""
+    from . import search as S
+    if "codes" not in search or set(search) - {"codes", "yaws", "keep", "rows"}:
+        raise ValueError("align_many: search must be a dict with 'codes' and, if wanted, 'yaws', 'keep' and 'rows' (got %r)" % (sorted(search),))
+    B, keep = len(params_list), int(search.get("keep", 2))
+    if samples is not None:
+        samples = [samples] if isinstance(samples, BoundSamples) else list(samples)
+    elif len(list(clouds)) != B:
+        raise ValueError("align_many: %d parameter sets, %d clouds" % (B, len(list(clouds))))
+    found = S.search_poses(dsdf, params_list, clouds, search["codes"], yaws=search.get("yaws", (0.0, float(np.pi))), keep=keep, samples=samples,
+                           rows=int(search.get("rows", kw["rows_per_iter"])), clamp=kw["clamp"], unit_latents=kw["unit_latents"], draw=kw["draw"],
+                           staging_bytes=kw["staging_bytes"], **view_kw)
+    fits = align_many(dsdf, [found.params[b][r] for b in range(B) for r in range(keep)], None, seed=view_kw["seed"],
+                      samples=[found.samples[b] for b in range(B) for _ in range(keep)], **kw)
+    unusable = torch.full_like(fits.flags, BAD_TABLE)
+    chosen = S.choose(fits.loss.reshape(B, keep), torch.where(found.valid.reshape(-1), fits.flags, unusable).reshape(B, keep))
+    at = torch.arange(B, device=chosen.device) * keep + chosen.clamp(min=0)
+    out = Aligned(fits.latents[at], fits.raw_latents[at], fits.theta[at], fits.loss[at], fits.flags[at],
+                  None if fits.history is None else fits.history[:, at], found.samples, fits.unit_latents)
+    out.found, out.chosen, out.fits = found, chosen, fits
+    return out

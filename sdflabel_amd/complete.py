@@ -155,14 +155,45 @@ def _view_rows(who, call, clouds, normals, origin, F, eta, s_max, seed, dev, pos
 
 @_lib.traced("fit_many")
 def fit_many(dsdf, samples, iters=800, rows_per_iter=8000, lr=5e-3, lr_step=None, lr_factor=0.1, clamp=0.1, code_reg=1e-4, unit_latents=True, init=None,
-             seed=0, history=False, staging_bytes=STAGING_BYTES, draw=None):
+             seed=0, history=False, staging_bytes=STAGING_BYTES, draw=None, *, search=None):
     """encode.encode_many for interval samples: fit one latent per shape to `samples` (a list of BoundSamples, or one) under the frozen
     decoder.  The keywords, the staging, the random stream and the returned Encoded are encode_many's; the loss of a row is the distance from
     the clamped prediction to the clamped interval, `.flags` bit 1 (2) means no row with a finite prediction and usable bounds.  On
-    BoundSamples.from_sdf(s) the results are encode_many's on s in every bit."""
+    BoundSamples.from_sdf(s) the results are encode_many's on s in every bit.
+
+    search: None, or a dict for search.search_many -- `codes` (a codebook [C][L]), `keep` (default 3), `rows` (default rows_per_iter) --:
+    the starts of every shape are scored and ranked first, the fit then runs on B x keep copies of the shapes from the kept starts (`init`
+    with a search is refused), and search.choose returns, per shape, the copy whose fit ended with the lowest loss.  The Encoded then holds the chosen
+    fits, `.found` the search.Found, `.chosen` int64 [B] the chosen rank (-1: none usable, rank 0 is returned) and `.fits` the Encoded of
+    all B x keep fits, shape-major.  The cost is the scoring pass plus keep times the fit."""
     samples = [samples] if isinstance(samples, BoundSamples) else list(samples)
+    if search is not None:
+        if init is not None:
+            raise ValueError("fit_many: give init or search, not both (with a search the fit starts from the found latents)")
+        return _fit_searched(dsdf, samples, dict(search), dict(iters=iters, rows_per_iter=rows_per_iter, lr=lr, lr_step=lr_step, lr_factor=lr_factor,
+                                                               clamp=clamp, code_reg=code_reg, unit_latents=unit_latents, seed=seed, history=history,
+                                                               staging_bytes=staging_bytes, draw=draw))
     fit = _Fit("fit_many", "sdfr_bound_rows", "sdfr_bound_reduce", 5, "x y z lo hi", "BoundSamples.load(path, device)", samples, lr, init, seed)
     return Encoded(*_fit(fit, dsdf, iters, rows_per_iter, lr_step, lr_factor, clamp, code_reg, unit_latents, seed, history, staging_bytes, draw))
+
+
+def _fit_searched(dsdf, samples, search, kw):
+    """fit_many with search=: search.search_many, the fit of every kept start, search.choose"""
+    from . import search as S
+    if "codes" not in search or set(search) - {"codes", "keep", "rows"}:
+        raise ValueError("fit_many: search must be a dict with 'codes' and, if wanted, 'keep' and 'rows' (got %r)" % (sorted(search),))
+    keep = int(search.get("keep", 3))
+    found = S.search_many(dsdf, samples, search["codes"], keep=keep, rows=int(search.get("rows", kw["rows_per_iter"])), clamp=kw["clamp"],
+                          unit_latents=kw["unit_latents"], seed=kw["seed"], draw=kw["draw"], staging_bytes=kw["staging_bytes"])
+    B = len(samples)
+    fits = fit_many(dsdf, [samples[b] for b in range(B) for _ in range(keep)], init=found.latents.reshape(B * keep, -1), **kw)
+    unusable = torch.full_like(fits.flags, BAD_TABLE)
+    chosen = S.choose(fits.loss.reshape(B, keep), torch.where(found.valid.reshape(-1), fits.flags, unusable).reshape(B, keep))
+    at = torch.arange(B, device=chosen.device) * keep + chosen.clamp(min=0)
+    enc = Encoded(fits.latents[at], fits.raw_latents[at], fits.loss[at], fits.flags[at], None if fits.history is None else fits.history[:, at],
+                  fits.unit_latents)
+    enc.found, enc.chosen, enc.fits = found, chosen, fits
+    return enc
 
 
 def _cloud_normals(cloud, radius=1.0, max_nn=30):
@@ -174,11 +205,11 @@ def _cloud_normals(cloud, radius=1.0, max_nn=30):
 
 
 @_lib.traced("complete_many")
-def complete_many(dsdf, params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0), free_rows=4, eta=0.01, s_max=0.5, seed=0, **fit_kw):
+def complete_many(dsdf, params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0), free_rows=4, eta=0.01, s_max=0.5, seed=0, *, search=None, **fit_kw):
     """A latent per annotation from its lidar cloud alone: view_samples_many, then fit_many.  params_list gives the pose (and, as the default
     `init`, the latent the fit starts from); normals=None estimates them with frame.lidar_normals on each cloud (NaN where a
-    point has fewer than 3 neighbours, so its normal rows are left out).  fit_kw: fit_many's keywords.  Returns the Encoded, with the rows
-    as `.samples`."""
+    point has fewer than 3 neighbours, so its normal rows are left out).  fit_kw: fit_many's keywords.  search: fit_many's -- the start then
+    comes from the scored codebook and not from the parameters' latent.  Returns the Encoded, with the rows as `.samples`."""
     params_list, clouds = list(params_list), list(clouds)
     dev = next(dsdf.parameters()).device
     if dev.type != "cuda":
@@ -187,7 +218,9 @@ def complete_many(dsdf, params_list, clouds, normals=None, origin=(0.0, 0.0, 0.0
         normals = [_cloud_normals(c if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)).to(dev)) if len(c) else
                    torch.zeros((0, 3), dtype=torch.float64, device=dev) for c in clouds]
     samples = view_samples_many(params_list, clouds, normals, origin, free_rows, eta, s_max, seed, _device=dev)
-    if fit_kw.get("init") is None and params_list:
+    if search is not None:
+        fit_kw["search"] = search
+    elif fit_kw.get("init") is None and params_list:
         from .verify import _pose_rows
         fit_kw["init"] = _pose_rows(params_list, dev)[1]
     fit_kw.setdefault("seed", seed)

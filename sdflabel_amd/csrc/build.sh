@@ -63,6 +63,7 @@ $HIPCC $COMMON -ffp-contract=off -c "$HERE/complete.hip" -o "$HERE/obj/complete.
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/align.hip" -o "$HERE/obj/align.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/cluster.hip" -o "$HERE/obj/cluster.o" &
 $HIPCC $COMMON -ffp-contract=off -c "$HERE/track.hip" -o "$HERE/obj/track.o" &
+$HIPCC $COMMON -ffp-contract=off -c "$HERE/search.hip" -o "$HERE/obj/search.o" &
 wait
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/${SDFR_LIBNAME:-libsdfr_hip.so}" "$HERE"/obj/{common,mlp,mlp_fwd32,mlp_fwd16,mlp_split,mlp_jac,mlp_jac16,mlp_persist,mlp_balance,mlp_small,mlp_ln,mlp_train,encode,complete,align,track,cluster,surface,band_rank,project,splat,params,losses,trace,pose,box_iou,detection_eval,frame,ingest,augment,normals,css_head,css_train,mesh,verify,crops,synth,mesh_sdf}.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/${SDFR_LIBNAME:-libsdfr_hip.so}" "$HERE"/obj/{common,mlp,mlp_fwd32,mlp_fwd16,mlp_split,mlp_jac,mlp_jac16,mlp_persist,mlp_balance,mlp_small,mlp_ln,mlp_train,encode,complete,align,track,search,cluster,surface,band_rank,project,splat,params,losses,trace,pose,box_iou,detection_eval,frame,ingest,augment,normals,css_head,css_train,mesh,verify,crops,synth,mesh_sdf}.o
 echo "built $OUT/${SDFR_LIBNAME:-libsdfr_hip.so}"

@@ -51,7 +51,14 @@ static int enc_samples_launch(const char* name, const float* points, const doubl
 // ---- rows -----------------------------------------------------------------------------------------------------------------------------------
 // grid (ceil(k / 256), B) -- or (1, B) without inputs: zn and flags only.  A workgroup writes 256 rows of one shape: thread tid draws row
 // s0 + tid, the row policy stores its side arrays and says what goes to LDS (the sample's index, or the position under the pose); then the
-// [256][L + 3] block is written element by element (consecutive threads, consecutive words).
+// [256][L + 3] block is written element by element (consecutive threads, consecutive words).  Workgroup b draws from the samples of shape
+// b, unless the policy has an owner(): then from that shape's (search_cells.h: many starts on one shape's samples; -1: none, which counts
+// as a broken table entry), while z, the policy's own arrays and every output stay indexed by b.
+template <class Rows>
+__host__ __device__ __forceinline__ auto enc_rows_owner(const Rows& rows, int b, int) -> decltype(rows.owner(b)) { return rows.owner(b); }
+template <class Rows>
+__host__ __device__ __forceinline__ int enc_rows_owner(const Rows&, int b, long) { return b; }
+
 template <class Rows>
 __global__ __launch_bounds__(ENC_THREADS) void enc_rows_kernel(const float* __restrict__ samples, int64_t S, const int64_t* __restrict__ soff, int shape0,
                                                               int64_t k, int draw, uint64_t seed, int64_t iter, const float* __restrict__ z, int L,
@@ -62,7 +69,8 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_rows_kernel(const float* __re
     __shared__ float s_zn[ENC_MAX_L];
     __shared__ float s_nrm;
     __shared__ typename Rows::Staged s_row[ENC_THREADS];
-    const int64_t count = enc_count(soff, b, S);
+    const int own = enc_rows_owner(rows, b, 0);
+    const int64_t count = own < 0 ? -1 : enc_count(soff, own, S);
     const bool bad = count < 0 || (!draw && inputs && count > 0 && k > count);
     const bool zero = bad || count == 0;
     const typename Rows::Shape shape = rows.shape(b);
@@ -79,7 +87,7 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_rows_kernel(const float* __re
     const int n = (int)((k - s0) < ENC_THREADS ? (k - s0) : ENC_THREADS);
     if (tid < n) {
         const int64_t s = s0 + tid;
-        const int64_t src = zero ? -1 : soff[b] + (draw ? enc_draw(seed, iter, shape0 + b, s, count) : s);
+        const int64_t src = zero ? -1 : soff[own] + (draw ? enc_draw(seed, iter, shape0 + own, s, count) : s);
         s_row[tid] = rows.stage(shape, samples, src, (int64_t)b * k + s);
     }
     __syncthreads();

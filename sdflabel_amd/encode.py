@@ -39,6 +39,7 @@ class Encoded:
         self.latents, self.raw_latents, self.loss, self.flags, self.history = latents, raw_latents, loss, flags, history
         self.unit_latents = unit_latents
         self.samples = None
+        self.found = self.chosen = self.fits = None        # complete.fit_many(search=...): the search.Found, the chosen rank, every kept start's fit
 
 
 def _upload(host, device):

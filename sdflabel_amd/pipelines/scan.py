@@ -36,7 +36,7 @@ def pinhole_extents(props, K):
     return ext[:, 6:10]
 
 
-def label_scan(dsdf, grid, lidar, K, w, h, world_to_cam, latent, remove_road=True, cluster_kw=None, align_kw=None):
+def label_scan(dsdf, grid, lidar, K, w, h, world_to_cam, latent, remove_road=True, cluster_kw=None, align_kw=None, *, search=None):
     """KITTI labels of one scan from the lidar and the shape prior `dsdf` alone.
 
     lidar [N][3], camera frame; K, w, h: the camera (the frustum of remove_road, the labels' 2-D boxes); world_to_cam: the 4x4 p_WC of
@@ -50,6 +50,10 @@ def label_scan(dsdf, grid, lidar, K, w, h, world_to_cam, latent, remove_road=Tru
     HOST SYNCHRONISATIONS: 2 + ceil(A / 16) for A accepted proposals -- one in proposals (counts, offsets, rectangles), one here (the 2-D
     boxes and the choice, one copy), one per chunk of 16 annotations in labels_many; remove_road and align_many make none.  With A == 0 it is
     the one of proposals.
+    search: None, or align_many's search dict (`codes`, `yaws`, `keep`, `rows`): steps 3 and 4 then are align_many(props.params, props.clouds,
+    search=search) -- search.search_poses over codes x yaw offsets on every proposal's box, the fit of the kept starts, search.choose --;
+    `latent` is not used as a start, stages['fits'] is that Aligned (with `.found`, `.chosen`, `.fits`), stages['second'] stays empty and
+    stages['chosen'] holds the chosen ranks on the host.  The synchronisations are the same.
     Returns (labels, stages): labels in the dict shape frame.frame_dict makes; stages = {'keep', 'proposals' (with its clusters and
     rectangles), 'fits' (the Aligned of the 2 A-batch, or None), 'second' (the choice, bool [A] on the host), 'params' (the chosen
     parameters, device tensors), 'bboxes', 'labels' (labels_many's tuples)}."""
@@ -59,13 +63,19 @@ def label_scan(dsdf, grid, lidar, K, w, h, world_to_cam, latent, remove_road=Tru
     stages = {"keep": keep, "proposals": props, "fits": None, "second": np.zeros(0, bool), "params": [], "bboxes": [], "labels": []}
     if A == 0:
         return FR.frame_dict([]), stages
-    fits = align_many(dsdf, props.params + props.flipped, props.clouds + props.clouds, **(align_kw or {}))
-    second = choose(fits.loss, A)
-    theta = torch.where(second[:, None], fits.theta[A:], fits.theta[:A])
-    lat = torch.where(second[:, None], fits.latents[A:], fits.latents[:A])
+    if search is not None:
+        fits = align_many(dsdf, props.params, props.clouds, search=search, **(align_kw or {}))
+        theta, lat, second = fits.theta, fits.latents, fits.chosen
+    else:
+        fits = align_many(dsdf, props.params + props.flipped, props.clouds + props.clouds, **(align_kw or {}))
+        second = choose(fits.loss, A)
+        theta = torch.where(second[:, None], fits.theta[A:], fits.theta[:A])
+        lat = torch.where(second[:, None], fits.latents[A:], fits.latents[:A])
     uv = pinhole_extents(props, K)
     host = torch.cat([uv.reshape(-1), second.float()]).cpu().numpy()                     # the one host read of this function
     uv, sec = host[:4 * A].reshape(A, 4), host[4 * A:] != 0
+    if search is not None:
+        stages["chosen"], sec = host[4 * A:].astype(np.int64), np.zeros(0, bool)
     bboxes = [np.array([np.clip(u0, 0, w), np.clip(v0, 0, h), np.clip(u1, 0, w), np.clip(v1, 0, h)], np.float32) for u0, u1, v0, v1 in uv]
     params = [{"yaw": theta[a, 0:1], "trans": theta[a, 1:4], "scale": theta[a, 4:5], "latent": lat[a]} for a in range(A)]
     labels = FR.labels_many(dsdf, grid, params, world_to_cam, bboxes)
