@@ -29,6 +29,16 @@ SDFR_KC_HD int sdfr_kc_rank(uint32_t w0, uint32_t w1, int q, int g) {
 // sdfr_kcm_pads' wave).  The compacted value image of tests/kc_epilogue_host: k list entry 0, zeros stored by the LAST wave
 SDFR_KC_HD int sdfr_kc_padded(int tot) { return (tot + 15) & ~15; }
 SDFR_KC_HD bool sdfr_kc_pads(int wave, int n_waves) { return wave == n_waves - 1; }
+// the chain steps the product EXECUTES (gemm_kc_body, full-width waves; host emulation: tests/kc_tail_host): chain step ks of k tile t reads
+// the positions 8 t + 2 ks and 8 t + 2 ks + 1 (component ks of both lane groups), so `tot` survivors are covered by ceil(tot / 2) steps.  The
+// k list, its pad entries and the ring's gathers keep the padded extent; the steps behind the last live one would only add fma(+0, w, acc).
+// Whole trips (SDFR_KC_TRIP_STEPS steps: two k tiles) run in the ring loop, the remaining 0 to 7 behind its exit from the two stages the
+// ring has already filled: step i of the tail is component i % 4 of stage i / 4.
+constexpr int SDFR_KC_TILE_STEPS = 4, SDFR_KC_TRIP_STEPS = 8;
+SDFR_KC_HD int sdfr_kc_steps(int tot) { return (tot + 1) >> 1; }
+SDFR_KC_HD int sdfr_kc_padded_steps(int tot) { return sdfr_kc_padded(tot) >> 1; }      // what the loop ran before the tail (SDFR_KC_TAIL=0)
+SDFR_KC_HD int sdfr_kc_trip_tiles(int steps) { return steps / SDFR_KC_TRIP_STEPS * 2; }  // k tiles the ring loop consumes
+SDFR_KC_HD int sdfr_kc_tail_steps(int steps) { return steps % SDFR_KC_TRIP_STEPS; }
 
 // The k-major image of the compacted operand (64-row tiles: two point tiles of 32).  The chain order, the ranks and the k list are the ones
 // above; only the place where a survivor's values wait for the product differs.  The survivor at chain position pos owns ROW pos of the

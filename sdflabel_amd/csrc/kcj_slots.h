@@ -49,6 +49,13 @@ SDFR_KCJ_HD int sdfr_kcj_padded(int tot) {
     const int p = (tot + trip - 1) / trip * trip;
     return p < trip ? trip : p;
 }
+// the k tiles the product EXECUTES (gemm_kcj; host emulation: tests/kc_tail_host): ceil(tot / 16), at least one.  The operand, the k list
+// and the ring's gathers keep the padded extent; the tiles behind the last live one would only add fma(+0, w, acc).  Whole trips run in the
+// ring loop, the remaining 0 to 3 tiles behind its exit from the stages the ring has already filled: tail tile u sits in stage u.
+SDFR_KCJ_HD int sdfr_kcj_tiles(int tot) { return tot <= SDFR_KCJ_KT ? 1 : (tot + SDFR_KCJ_KT - 1) / SDFR_KCJ_KT; }
+SDFR_KCJ_HD int sdfr_kcj_padded_tiles(int tot) { return sdfr_kcj_padded(tot) / SDFR_KCJ_KT; }   // what the loop ran before the tail (SDFR_KC_TAIL=0)
+SDFR_KCJ_HD int sdfr_kcj_trip_tiles(int tiles) { return tiles / SDFR_KCJ_RING * SDFR_KCJ_RING; }
+SDFR_KCJ_HD int sdfr_kcj_tail_tiles(int tiles) { return tiles % SDFR_KCJ_RING; }
 // padding: element e of the pad block (16 points per slot) -> chain position and point
 SDFR_KCJ_HD int sdfr_kcj_pad_pos(int tot, int e) { return tot + e / SDFR_KCJ_PT; }
 SDFR_KCJ_HD int sdfr_kcj_pad_point(int e) { return e % SDFR_KCJ_PT; }

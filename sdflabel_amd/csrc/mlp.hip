@@ -53,6 +53,7 @@ extern "C" int sdfr_decoder_create(sdfr_decoder** out, int n_lin, const int* in_
     int64_t off_f = 0, off_b = 0, off_h = 0, off_s = 0, off_bh = 0;
     const bool kinj = (n_inputs <= 8) && (HP == 512);
     P.kinj = kinj ? 1 : 0;
+    P.kc_tail = 1;          // (the launchers of the compacted kernels clear it for SDFR_KC_TAIL=0)
     for (int l = 0; l < n_lin; ++l) {
         MlpLayer& L = P.L[l];
         L.in_dim = in_dim[l]; L.out_dim = out_dim[l]; L.inj_n = inj_n[l]; L.inj_off = inj_off[l];

@@ -24,6 +24,10 @@ static void fwd_env(MlpParams& Q) {
     // (=2, tests only: the compaction even where the decoder's finite check declined it -- right only while every non-finite weight sits in
     // a k row that no survivor and no pad entry names; tests/test_gpu_kc_dense.py shows with it that the row of a dead feature is never read)
     else if (e && e[0] == '2' && Q.Wk) Q.kcompact = 1;
+    //   SDFR_KC_TAIL=0       the compacted products run their whole padded extent instead of stopping behind the last chain step that holds
+    //                        a survivor (kc_slots.h, sdfr_kc_steps); same bits
+    const char* t = getenv("SDFR_KC_TAIL");
+    if (t && t[0] == '0') Q.kc_tail = 0;
 }
 void sdfr_launch_fwd_f32_512(const MlpParams& P, int64_t n, bool save_masks, hipStream_t s) {
     static_assert(SDFR_FWD_FT * SDFR_FWD_NW == 16, "padded width 512 = 32 * FT * NW");

@@ -59,6 +59,10 @@ void sdfr_launch_jac_f32_512(const MlpParams& P, int cap, int B, bool from_masks
         // (kcjd_slots.h) -- the same places, the same bits
         const char* st = getenv("SDFR_JAC_STAGE");
         if (st && st[0] == '0' && Q.jcompact) Q.jcompact = 1;
+        // SDFR_KC_TAIL=0 (read at every launch): the compacted products run whole trips of four k tiles instead of stopping behind the last
+        // k tile that holds a survivor (kcj_slots.h, sdfr_kcj_tiles) -- the same bits
+        const char* kt = getenv("SDFR_KC_TAIL");
+        if (kt && kt[0] == '0') Q.kc_tail = 0;
         hipLaunchKernelGGL((sdfr_mlp_kernel<float, 16, SDFR_JAC_SMALL_FT, 1, SDFR_JAC_SMALL_NW, SDFR_JAC_SMALL_PF, 3>), dim3(sdfr_cdiv(cap, 16), B),
                            dim3(64 * SDFR_JAC_SMALL_NW), 0, s, Q);
     }

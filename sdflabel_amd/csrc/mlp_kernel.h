@@ -125,6 +125,8 @@ struct MlpParams {
                                  // (sdfr_mlp_forward_balanced)
     unsigned long long* tile_trace;   // builds with -DSDFR_MLP_TRACE: per-workgroup records of the forward kernels (sdfr_debug_set_tile_trace,
     int64_t tile_trace_cap;           // SDFR_TILE_TRACE_WORDS words each, workgroups >= tile_trace_cap write nothing), else unused
+    int kc_tail;                 // != 0: the compacted products (KC, KCJ) stop behind the last chain step / k tile that holds a survivor (kc_slots.h
+                                 // sdfr_kc_steps, kcj_slots.h sdfr_kcj_tiles); 0: they run the whole padded extent (SDFR_KC_TAIL=0) -- the same bits
 };
 // One record of the tile trace (tools/tile_gantt.py): shader clock at the workgroup's start and end, the 100 MHz constant clock at both (the
 // shader clocks of two XCDs need not agree; the constant clock orders tiles across the device), where it ran, and blockIdx.x.
@@ -834,8 +836,9 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
     // 4-byte gather per feature tile the loop ran 13 % short of its matrix rate); the k list is read from LDS ahead of the gather it
     // feeds.  Ring of two tiles and clamped prefetch indices, as in gemm_body's branch-free loop (full-width waves: refilled component by
     // component, two tiles ahead -- the ring rule of kc_slots.h).  The VALUES of slot s wait in the row of the dense image that the slot's
-    // k word names (kc_slots.h, sdfr_kcd_*), pads in the zero row.
-    auto gemm_kc_body = [&](const float* __restrict__ Wl, int nk, int nact, auto full_tag) {
+    // k word names (kc_slots.h, sdfr_kcd_*), pads in the zero row.  nsteps: the chain steps (KV per k tile) the full-width product executes --
+    // the survivors' sdfr_kc_steps, or all nk / 2 of them (P.kc_tail == 0); the k list, the gathers and the narrow waves keep nk.
+    auto gemm_kc_body = [&](const float* __restrict__ Wl, int nk, int nsteps, int nact, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
         const int nkt = nk / KT;
         if (nkt <= 0) return;
@@ -925,7 +928,12 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
 #pragma unroll
                     for (int r = 0; r < RG * 4; ++r) acc[f][p][r] = 0.f;
             __builtin_amdgcn_sched_barrier(0);
-            for (int t = 0; t < nkt; t += SDFR_KC_RING_STAGES) {
+            // The loop runs the WHOLE trips of the nsteps chain steps that hold a survivor (sdfr_kc_steps); the 0 to 7 steps left over follow
+            // its one exit, each under a wave-uniform guard, from the two stages the ring has filled by then (the last trip's gathers, or
+            // the prologue's: tiles ntrip and ntrip + 1 <= nkt - 1).  The chain steps behind them meet pad entries only:
+            // fma(+0, w, acc) == acc while the pad row's weights are finite and acc is not -0 -- what the compaction already asks of dead features.
+            const int ntrip = sdfr_kc_trip_tiles(nsteps);
+            for (int t = 0; t < ntrip; t += SDFR_KC_RING_STAGES) {
 #pragma unroll
                 for (int u = 0; u < SDFR_KC_RING_STAGES; ++u) {
                     const int s = sdfr_kc_ring_stage(u);
@@ -938,6 +946,12 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
                     }
                     ko[s] = klp[sdfr_kc_ring_klist_tile(t + u, nkt) * NLG];
                 }
+            }
+            const int rem = sdfr_kc_tail_steps(nsteps);
+#pragma unroll
+            for (int i = 0; i < SDFR_KC_TRIP_STEPS - 1; ++i) {
+                if (rem > i) mma1(a[i / SDFR_KC_TILE_STEPS], b[i / SDFR_KC_TILE_STEPS], i % SDFR_KC_TILE_STEPS);
+                __builtin_amdgcn_sched_barrier(0);
             }
             return;
         }
@@ -962,7 +976,7 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    auto gemm_kc = [&](auto Wl, int nk, int rows_active) {            // (generic: instantiated by KC kernels only)
+    auto gemm_kc = [&](auto Wl, int nk, int nsteps, int rows_active) {            // (generic: instantiated by KC kernels only)
         int nact = (rows_active - fbase + MS - 1) / MS;
         nact = nact < 0 ? 0 : (nact > FT ? FT : nact);
         nact = __builtin_amdgcn_readfirstlane(nact);
@@ -975,15 +989,16 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
 #pragma unroll
                     for (int r = 0; r < RG * 4; ++r) acc[f][p][r] = 0.f;
         }
-        if (nact == FT) gemm_kc_body(Wl, nk, FT, std::true_type{});
-        else if (nact > 0) gemm_kc_body(Wl, nk, nact, std::false_type{});
+        if (nact == FT) gemm_kc_body(Wl, nk, nsteps, FT, std::true_type{});
+        else if (nact > 0) gemm_kc_body(Wl, nk, nsteps, nact, std::false_type{});
     };
     // KCJ product: the operand holds nk compacted chain positions (whole trips of SDFR_KCJ_RING k tiles), in the layout the full chain reads.
     // Component s of lane group lg in k tile t meets row kcj_list4[4 t + lg][s] of the k-major image Wkj, where the lane's eight feature-tile
     // values are contiguous (sdfr_kcj_col): two 16-byte gathers per component, eight per tile as in the full chain, the address a 32-bit
     // offset on the wave-uniform layer image.  The ring of kcj_slots.h: weights three tiles ahead, their k-list words one tile before that,
     // clamped indices, one block per trip.  (Every wave is full width: the launcher selects the compaction only for hidden in-widths of HP.)
-    auto gemm_kcj = [&](const float* __restrict__ Wl, int nk) {
+    // ntiles: the k tiles the product executes -- the survivors' sdfr_kcj_tiles, or all nk / KT of them (P.kc_tail == 0).
+    auto gemm_kcj = [&](const float* __restrict__ Wl, int nk, int ntiles) {
         if constexpr (KCJ) {
         const int nkt = nk / KT;
         const uint32_t wlane4 = (uint32_t)(fbase + 8 * lp) * 4u;
@@ -1011,7 +1026,12 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[f][0][r] = 0.f;
         __builtin_amdgcn_sched_barrier(0);
-        for (int t = 0; t < nkt; t += SDFR_KCJ_RING) {
+        // The loop runs the WHOLE trips of the ntiles k tiles that hold a survivor (sdfr_kcj_tiles); the 0 to 3 tiles left over follow its one
+        // exit, each under a wave-uniform guard: their weights wait in stages 0 to 2 (the last trip's gathers, or the prologue's: tiles ntrip
+        // to ntrip + 2 <= nkt - 1), tile ntrip's operand in b[0], and the operands of the other two are read here.  The tiles behind them
+        // hold pad rows only: fma(+0, w, acc) == acc while the weights are finite and acc is not -0, as for the features the compaction skips.
+        const int ntrip = sdfr_kcj_trip_tiles(ntiles);
+        for (int t = 0; t < ntrip; t += SDFR_KCJ_RING) {
 #pragma unroll
             for (int u = 0; u < SDFR_KCJ_RING; ++u) {
                 load_a(ko, a[(u + SDFR_KCJ_RING - 1) % SDFR_KCJ_RING]);       // (tile sdfr_kcj_ring_gather_tile(t + u): its words are in ko)
@@ -1025,6 +1045,19 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
                         acc[f][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(a[u][ks][f >> 2], f & 3), f4c(b[u % 2], ks), acc[f][0], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
+        }
+        const int rem = sdfr_kcj_tail_tiles(ntiles);
+#pragma unroll
+        for (int u = 0; u < SDFR_KCJ_RING - 1; ++u) {
+            if (rem > u) {
+                if (u + 1 < SDFR_KCJ_RING - 1) b[(u + 1) % 2] = bptr[(ntrip + u + 1) * (NLG * PT)];
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                    for (int f = 0; f < FT; ++f)
+                        acc[f][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(a[u][ks][f >> 2], f & 3), f4c(b[u % 2], ks), acc[f][0], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
         }
         }
     };
@@ -1113,7 +1146,8 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
     // ---- forward through the MFMA layers -------------------------------------------------------------------
     int* t_more = reinterpret_cast<int*>(gy);           // gy is unused by forward modes
     const bool kc_on = KC && P.kcompact && P.Wk;
-    int kc_n = 0;                                       // KC: compacted K extent of the operand the next product reads
+    int kc_s = 0;                                       // KC: chain steps the next product executes (kc_slots.h, sdfr_kc_steps); the K extent of
+                                                        // its operand and k list is sdfr_kc_padded(2 kc_s) = sdfr_kc_padded(survivors)
     if constexpr (KC) {
         // the zero row of the dense image, written once per workgroup (layer 0's barriers lie between this store and its first reader)
         if (kc_on && tid < KZ4) lds4[KGX * PT + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1127,7 +1161,7 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
         const bool kc_in = kc_on && l > 0, kc_out = kc_on && l + 1 < P.n_mfma;
         SDFR_STAMP(l, 0);
         if constexpr (KC) {
-            if (kc_in) gemm_kc(P.Wk + (int64_t)L.off_f * 4, kc_n, L.out_dim);
+            if (kc_in) gemm_kc(P.Wk + (int64_t)L.off_f * 4, sdfr_kc_padded(2 * kc_s), kc_s, L.out_dim);
             else gemm(Wfwd + L.off_f, L.kp_f, L.out_dim);
         } else gemm(Wfwd + (HALF ? L.off_h : L.off_f), HALF ? L.kp_h : L.kp_f, L.out_dim);
         SDFR_STAMP(l, 1);
@@ -1252,7 +1286,7 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
             if (sdfr_kcm_pads(wave)) {
                 if (lane < padded - tot) reinterpret_cast<int*>(kc_list4)[sdfr_kc_slot(tot + lane)] = sdfr_kcd_pad_entry();
             }
-            kc_n = padded;
+            kc_s = P.kc_tail ? sdfr_kc_steps(tot) : sdfr_kc_padded_steps(tot);
             // ORDER: what this layer's operand adds to the tile's cost (tile_balance.h).  Thread 0 alone zeroes, adds to and reads the word;
             // the add is written as an LDS atomic all the same, for the instruction it gives: one ds_add_u32 without a result.  A plain
             // rows[127] += ... is a read, an add and a write through a VGPR in the middle of the epilogue, and the register allocator
@@ -1563,7 +1597,8 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
     const bool kcj_on = KCJ && P.jcompact && P.Wkj;
     const bool kcj_fast = P.jcompact >= 2;              // the survivors in chain order as well (kcjd_slots.h): kcj_c[j] bit 4 (q % 8) + g = kcj_w[g] bit 8 j + q % 8
     uint32_t kcj_w[4] = {0u, 0u, 0u, 0u}, kcj_c[4] = {0u, 0u, 0u, 0u};
-    int kcj_n = 0;                                      // compacted K extent of the operand the next product reads
+    int kcj_t = 0;                                      // k tiles the next product executes (kcj_slots.h, sdfr_kcj_tiles); the K extent of its
+                                                        // operand and k list is sdfr_kcj_padded(16 kcj_t) = sdfr_kcj_padded(survivors)
     auto kcj_vote = [&](int l, const uint32_t* raw) {
         const int prev_out = P.L[l - 1].out_dim;
         uint32_t m = 0u;
@@ -1836,7 +1871,7 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
                     act_e[sdfr_kcj_elem(pos, sdfr_kcj_pad_point(e))] = 0.f;
                     if (sdfr_kcj_pad_point(e) == 0) reinterpret_cast<int*>(kcj_list4)[sdfr_kcj_kidx(pos)] = 0;
                 }
-                kcj_n = padded;
+                kcj_t = P.kc_tail ? sdfr_kcj_tiles(tot) : sdfr_kcj_padded_tiles(tot);
                 return;
             }
         }
@@ -1997,7 +2032,7 @@ __global__ __launch_bounds__(64 * NW, SDFR_MLP_WPE) void sdfr_mlp_kernel(const M
         bool kcj_l = false;                                // KCJ: this product reads a compacted operand; the next one's survivors are voted on
         if constexpr (KCJ) kcj_l = kcj_on && l >= 1;
         if constexpr (KCJ) {
-            if (kcj_l) gemm_kcj(P.Wkj + (int64_t)L.off_b * 4, kcj_n);
+            if (kcj_l) gemm_kcj(P.Wkj + (int64_t)L.off_b * 4, sdfr_kcj_padded(SDFR_KCJ_KT * kcj_t), kcj_t);
         }
         if (!kcj_l)
         gemm(reinterpret_cast<const vec_t*>(HALF ? (const void*)P.Wbh : (const void*)P.Wb) + (HALF ? L.off_bh : L.off_b), HALF ? L.kp_bh : L.kp_b,
